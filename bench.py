@@ -10,6 +10,17 @@ one hipGraph replay per token, the token fed back on the device.
 Weights: random-init with the exact gemma-3-4b-it-q4_0 architecture (no
 checkpoints offline); prompt: seeded synthetic token ids.
 
+A plain run (--gpus 1 --steps N --warmup W) builds the model, prefills, warms
+up, times the N steps and prints the result line: value, ms_per_step and the
+HBM figures that follow from them.  --dump-outputs DIR also writes the greedy
+ids the timed steps returned (DIR/tokens.npy) and the logits of the position
+after them (DIR/next_logits.npy); the same arguments give the same inputs, so
+two builds can be compared output for output.  --full adds, after the
+timed steps, everything that takes runs of its own: per-family kernel timing
+and the roofline, the warm prefill, the exact-mode session, the CPU baseline
+and the parity check against the reference (--no-exact / --no-cpu-baseline
+drop those two legs of it).
+
 Single process per GPU.  With --gpus N (torchrun) the default is the north
 star's row-sharded decode: ONE greedy stream, each rank holding 1/N of every
 projection's output rows, slices all-gathered over RCCL after each projection
@@ -41,13 +52,22 @@ def parse():
     p.add_argument("--prefill", type=int, default=512)
     p.add_argument("--config", default="gemma-3-4b")
     p.add_argument("--exact", action="store_true")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything else the bench measures or checks: per-family "
+                        "kernel timing + roofline, the warm prefill, the exact-mode session, the CPU baseline and "
+                        "the parity check against the reference (a plain run prints the headline line only)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps write DIR/tokens.npy (float64: the greedy ids the timed steps "
+                        "returned) and DIR/next_logits.npy (float32: one untimed forward of the last id over the "
+                        "KV cache they wrote)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
     p.add_argument("--no-exact", action="store_true",
-                   help="skip the exact-mode sub-measurement (the reference's operation order: bit-exact greedy ids)")
+                   help="--full: skip the exact-mode sub-measurement (the reference's operation order: bit-exact "
+                        "greedy ids)")
     p.add_argument("--full-logits", action="store_true",
                    help="decode loop: full F16 logits GEMV + argmax instead of int8 screening + exact rescoring")
-    p.add_argument("--cpu-decode", type=int, default=32, help="decode tokens in the CPU baseline sample")
-    p.add_argument("--kernel-reps", type=int, default=2)
+    p.add_argument("--cpu-decode", type=int, default=32, help="--full: decode tokens in the CPU baseline sample")
+    p.add_argument("--kernel-reps", type=int, default=2, help="--full: launches per family in the kernel timing")
     p.add_argument("--no-graph", action="store_true", help="eager launches (for kernel tracers)")
     p.add_argument("--exchange", choices=["push", "rccl"], default="push",
                    help="tp: the one-shot push all-gather over IPC-mapped mailboxes (k_exchange.hip) or RCCL")
@@ -454,41 +474,60 @@ def main():
     value = a.steps * (1 if tp else d.world) / el
     ms = el * 1000.0 / a.steps
 
-    # Per-family kernel time of the timed graph: every family relaunched with
-    # its decode-step arguments, one launch per layer in decode order, each
-    # timed by events its own dispatch signals (Model.time_kernel); the
-    # dominant family by time per token is the roofline kernel.  The attention
-    # block reads the KV history at the position the decode loop ended on.
+    def dump_outputs():
+        """tokens.npy: what the timed enqueue + sync returned, one greedy id per timed step.  A random-init model
+        soon repeats one id, so next_logits.npy goes with it: the logits of one untimed forward of the last timed
+        id at the next position, over the KV cache the timed steps wrote (every rank of a tensor-parallel group
+        takes part in that forward; rank 0 writes)."""
+        lg = m.forward(np.array([toks[-1]], np.int32), pos + a.steps)
+        if d.rank == 0:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "tokens.npy"), np.asarray(toks, np.float64))
+            np.save(os.path.join(a.dump_outputs, "next_logits.npy"), lg)
+
+    if a.dump_outputs and not a.full:
+        dump_outputs()
+    # Everything below that launches or runs anything more is behind --full; a plain run prints its line from
+    # what the timed steps gave.
     L = info.n_layer
     fams = {}
-    in_graph = {0: True, 3: True, 4: True, 2: bool(info.screened_logits)}
-    for name, which, per_tok, kern in (("attention_block", 0, L, "attn_block_kernel"),
-                                       ("gate_up", 3, L, "gemv_q4_0_layer"),
-                                       ("down", 4, L, "gemv_q4_0_layer"),
-                                       ("token_selection", 2, 1, "screen_gemv_kernel")):
-        if not in_graph[which]:  # only the families the timed graph launches
-            continue
-        progress(f"kernel timing: {name}")
-        us_f, by_f = m.time_kernel(which, a.kernel_reps if which != 2 else 8)
-        if us_f <= 0:
-            continue
-        fams[name] = {"us_per_launch": round(us_f, 3), "launches_per_token": per_tok,
-                      "us_per_token": round(us_f * per_tok, 1), "bytes_per_launch": int(by_f),
-                      "GBps": round(by_f / (us_f * 1e-6) / 1e9, 1),
-                      "frac": round(by_f / (us_f * 1e-6) / 1e9 / PEAK_HBM_GBS, 4), "kernel": kern}
-    us_l, by_l = m.time_kernel(1, 2)
-    # the prompt once more on the same session: the prefill warm (prefill_s above is the session's first call, which
-    # also pays each prefill kernel's first launch)
-    t0 = time.time()
-    m.forward(prompt, 0, want_logits=False)
-    t_prefill_warm = time.time() - t0
-    dom_name = max(fams, key=lambda k: fams[k]["us_per_token"]) if fams else None
-    dom = fams.get(dom_name, {})
-    kpat = {"attention_block": "attn_block_kernel", "gate_up": "gemv_q4_0_layer<8, 10, 10",
-            "down": "gemv_q4_0_layer<1, 10, 5", "token_selection": "screen_gemv_kernel"}.get(dom_name, "-")
-    # the attention block's position-dependent stream: K and V rows of every kv head, per key attended
-    kv_key = info.kv_bytes_per_pos / L if dom_name == "attention_block" else 0.0
-    traffic, traffic_src = pmc_traffic(kpat, pmc_key(a), kv_key)
+    dom_name, dom, traffic, traffic_src = None, {}, None, None
+    if a.full:
+        # Per-family kernel time of the timed graph: every family relaunched with
+        # its decode-step arguments, one launch per layer in decode order, each
+        # timed by events its own dispatch signals (Model.time_kernel); the
+        # dominant family by time per token is the roofline kernel.  The attention
+        # block reads the KV history at the position the decode loop ended on.
+        in_graph = {0: True, 3: True, 4: True, 2: bool(info.screened_logits)}
+        for name, which, per_tok, kern in (("attention_block", 0, L, "attn_block_kernel"),
+                                           ("gate_up", 3, L, "gemv_q4_0_layer"),
+                                           ("down", 4, L, "gemv_q4_0_layer"),
+                                           ("token_selection", 2, 1, "screen_gemv_kernel")):
+            if not in_graph[which]:  # only the families the timed graph launches
+                continue
+            progress(f"kernel timing: {name}")
+            us_f, by_f = m.time_kernel(which, a.kernel_reps if which != 2 else 8)
+            if us_f <= 0:
+                continue
+            fams[name] = {"us_per_launch": round(us_f, 3), "launches_per_token": per_tok,
+                          "us_per_token": round(us_f * per_tok, 1), "bytes_per_launch": int(by_f),
+                          "GBps": round(by_f / (us_f * 1e-6) / 1e9, 1),
+                          "frac": round(by_f / (us_f * 1e-6) / 1e9 / PEAK_HBM_GBS, 4), "kernel": kern}
+        us_l, by_l = m.time_kernel(1, 2)
+        if a.dump_outputs:  # after the kernel timing, which runs at the position the decode loop ended on
+            dump_outputs()
+        # the prompt once more on the same session: the prefill warm (prefill_s above is the session's first call,
+        # which also pays each prefill kernel's first launch)
+        t0 = time.time()
+        m.forward(prompt, 0, want_logits=False)
+        t_prefill_warm = time.time() - t0
+        dom_name = max(fams, key=lambda k: fams[k]["us_per_token"]) if fams else None
+        dom = fams.get(dom_name, {})
+        kpat = {"attention_block": "attn_block_kernel", "gate_up": "gemv_q4_0_layer<8, 10, 10",
+                "down": "gemv_q4_0_layer<1, 10, 5", "token_selection": "screen_gemv_kernel"}.get(dom_name, "-")
+        # the attention block's position-dependent stream: K and V rows of every kv head, per key attended
+        kv_key = info.kv_bytes_per_pos / L if dom_name == "attention_block" else 0.0
+        traffic, traffic_src = pmc_traffic(kpat, pmc_key(a), kv_key)
     # the timed steps decode positions pos .. pos + steps - 1; the step at
     # position p attends to p + 1 keys, so the mean KV history read is
     # pos + (steps + 1) / 2 keys per layer
@@ -569,13 +608,13 @@ def main():
             "us_per_launch": dom["us_per_launch"], "bytes_per_launch": dom["bytes_per_launch"],
             "position": pos_end, "keys_attended": pos_end + 1, "pmc_key": pmc_key(a),
         } if dom else None),
-        "kernel_families": fams,
-        "logits_gemv": {"us": round(us_l, 2), "GBps": round(by_l / (us_l * 1e-6) / 1e9, 1)},
+        **({"kernel_families": fams,
+            "logits_gemv": {"us": round(us_l, 2), "GBps": round(by_l / (us_l * 1e-6) / 1e9, 1)}} if a.full else {}),
         "token_selection_mode": ("int8 screening + exact f16 rescoring of the candidates (ids = full F16 GEMV argmax)"
                                  if info.screened_logits else "full F16 logits GEMV + argmax"),
         "timing_detail": {"synthetic_build_s": round(t_build, 1), "prefill_s": round(t_prefill, 4),
                           "prefill_tokens_per_s": round(a.prefill / t_prefill, 1),
-                          "prefill_warm_s": round(t_prefill_warm, 4),
+                          **({"prefill_warm_s": round(t_prefill_warm, 4)} if a.full else {}),
                           "prefill_mode": ({7: "batched f16-MFMA (GEMM v7 gate_up, v6 qkv / o / down; f16 rows of the "
                                                 "dequantized Q8_0 activations)", 6: "batched f16-MFMA (v6, K-quants)",
                                             5: "batched int8-MFMA (GEMM v5, Q8_0 activation blocks)"}
@@ -590,9 +629,10 @@ def main():
     # same timed decode; its logits on the parity fixture's inputs are checked against the reference's own
     # (cpu_baseline, below).  Single GPU only.
     gpu_forced = {}
-    if d.world == 1 and not a.no_cpu_baseline:  # this session's logits on the parity fixture's inputs
+    cpu_leg = a.full and not a.no_cpu_baseline  # the CPU baseline and the parity check against it
+    if d.world == 1 and cpu_leg:  # this session's logits on the parity fixture's inputs
         gpu_forced["exact" if a.exact else "fast"] = forced_logits(m, prompt, cfg.vocab)
-    if d.world == 1 and not a.exact and not a.no_exact:
+    if d.world == 1 and a.full and not a.exact and not a.no_exact:
         progress("exact-mode session")
         mx = Model(g, device=dev, exact=True, max_ctx=max_ctx, use_graph=not a.no_graph)
         t0 = time.time()
@@ -610,7 +650,7 @@ def main():
         mx.sync(a.steps)
         el_x = time.perf_counter() - t0
         xinfo = mx.get_info()
-        gpu_forced["exact"] = forced_logits(mx, prompt, cfg.vocab) if not a.no_cpu_baseline else None
+        gpu_forced["exact"] = forced_logits(mx, prompt, cfg.vocab) if cpu_leg else None
         mx.close()
         out["exact"] = {
             "value": round(a.steps / el_x, 3), "unit": "tokens/s", "steps": a.steps,
@@ -622,7 +662,7 @@ def main():
             "how": "a second session with LLMI_EXACT (bit-identical to the reference's logits: "
                    "parity_vs_reference.exact), the same prompt, then the same timed decode"}
     parity_ok = True
-    if d.rank == 0 and d.world == 1 and not a.no_cpu_baseline:
+    if d.rank == 0 and d.world == 1 and cpu_leg:
         m.close()
         try:
             progress("cpu baseline (the reference on the host cores)")

@@ -25,7 +25,7 @@ want tests && run pytest_gpu 1000 python -u -m pytest tests -m gpu -x -v -rP -p 
 want smoke && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 want sweep && run gemv_sweep 300 scripts/gemv_sweep 200
 want ablate && run ablate_run 900 bash scripts/ablate.sh
-want bench && run bench 900 python bench.py
+want bench && run bench 900 python bench.py --full
 if want prof; then  # the timed decode graph itself (hipGraph replay), after a 512-token prefill
   run rocprof 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- \
     python3 bench.py --steps 64 --warmup 4 --prefill 512 --no-cpu-baseline
@@ -35,7 +35,7 @@ if want pmc; then  # FETCH_SIZE of the launches the bench line times, 2 reps, at
   for spec in "784 768 2 14" "537 512 5 20"; do
     set -- $spec
     run pmc_fetch_$1 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch_$1 -o run -- \
-      python3 bench.py --prefill $2 --warmup $3 --steps $4 --no-cpu-baseline
+      python3 bench.py --prefill $2 --warmup $3 --steps $4 --full --no-cpu-baseline
     python3 scripts/pmc_summary.py gpurun_out/pmc_fetch_$1/run_counter_collection.csv \
       gpurun_out/pmc_fetch_summary_$1.json gemma-3-4b/q4_0/pos$1/reps2 68 > gpurun_out/pmc_summary_$1.log 2>&1
   done
