@@ -215,7 +215,9 @@ typedef struct {
                                  push fused into the decode launches (the default push mode) */
   long long block_slow_waits; /* attention-block hand-off waits (per wave) that took over 20 us, since creation */
   int exact_engine;           /* 1: LLMI_EXACT runs on the exact-order engine (k_exact.hip: the reference's
-                                 arithmetic with streamed GEMVs and fused norms), 0: the per-op exact kernels */
+                                 arithmetic with streamed GEMVs and fused norms; Gemma-3 layers whose projections are
+                                 each Q4_0 or Q8_0, q/k/v of one type and gate/up of one type; tensor-parallel
+                                 sessions: Q4_0 only), 0: the per-op exact kernels */
   int exact_batched_prefill;  /* 1: an exact session runs a prompt's tokens before the last layer by layer, T at a
                                  time (the reference's chains per (row, token)), then the last as a decode step */
   int prefill_gemm;           /* the batched prefill's GEMM: 7 f16 MFMA on f16 rows of the dequantized Q8_0 activation

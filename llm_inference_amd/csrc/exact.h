@@ -12,6 +12,17 @@
 //   qs [g][row][jj] 16 B = bytes 4jj..4jj+3 of the four blocks' 16-B quants
 //   d  [g][row]     8 B  = the four blocks' f16 scales
 // so one wave-instruction of a group reads 16 rows x 64 B = 1 KB contiguous.
+//
+// The reference's Q8_0 row (ops.cpp:806-824) is one fp32 chain over the row's blocks in order,
+//   sum = fmaf((float)dot_b * f16(w.d_b), f16(x.d_b), sum),
+// whose products p_b = (float)dot_b * f16(w.d_b) (an exact integer dot, one rounded multiply) depend on nothing
+// before them: all lanes of a work-group compute them, then one lane per row runs the chain.
+//
+// XL layout of a Q8_0 weight [rows][nb] (nb % 4 == 0), group g = blocks 4g..4g+3:
+//   qs [g][row] 128 B = the four blocks' 32 int8 quants, block after block
+//   d  [g][row] 8 B   = the four blocks' f16 scales
+// so one wave-instruction of a group reads 8 rows x 8 lanes x 16 B = 1 KB contiguous (lane l of a row: half l & 1
+// of block l >> 1).
 #pragma once
 
 #include "session_kernels.h"
@@ -23,10 +34,12 @@ struct XlWeight {
   uint2* d = nullptr;
   int rows = 0, nb = 0;
   size_t bytes = 0;  // algorithmic (GGUF) bytes
+  uint32_t type = T_Q4_0;  // T_Q4_0 or T_Q8_0: which of the two layouts above qs holds
 };
 
-// sources of an XL weight: rows [0, n) of each device Q4_0 weight (row-major blocks), concatenated, or (gelu32)
-// two weights gate / up interleaved in groups of 32 rows (gate 32 k.., up 32 k..) for the GELU epilogue
+// sources of an XL weight: rows [0, n) of each device Q4_0 / Q8_0 weight (row-major blocks; one type for all the
+// sources), concatenated, or (gelu32) two weights gate / up interleaved in groups of 32 rows (gate 32 k.., up 32 k..)
+// for the GELU epilogue
 struct XlSrc {
   const DevWeight* w[3] = {nullptr, nullptr, nullptr};
   int n = 0;

@@ -1,7 +1,8 @@
-// k_exact.hip -- the exact-order engine's Q4_0 GEMVs (exact.h): the
-// reference's operation order (ops.cpp:364-399 mat_vec_mul_q4_0, ops.cpp:28-43
+// k_exact.hip -- the exact-order engine's Q4_0 and Q8_0 GEMVs (exact.h): the
+// reference's operation order (ops.cpp:364-399 mat_vec_mul_q4_0, ops.cpp:806-824 the Q8_0 row, ops.cpp:28-43
 // rms_norm, ops.cpp:116-139 quantize_row_q8_0, model.cpp:843-924 residual /
 // norm / GELU) with the weights streamed like the fast path's layer GEMVs.
+#include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
 
@@ -244,18 +245,116 @@ __device__ __forceinline__ void xl_eat1(const XlChunk& c, int g0, int ng, int jj
   }
 }
 
+// the GELU role's epilogue (every weight type): rows [0, 32) gate, [32, 64) up of the work-group's units 32 u ..
+// 32 u + 31 (model.cpp:892-899), their Q8_0 block (ops.cpp:116-139); threads 0-31
+__device__ __forceinline__ void xl_gelu_store(const float* s_rows, const XlArgs& a, int t) {
+  const float gv = gelu_mul1<true>(s_rows[t], s_rows[32 + t]);
+  a.hid[blockIdx.x * 32 + t] = gv;
+  q8_block_store(gv, true, a.hq + blockIdx.x, t);
+}
+
+// ---- Q8_0 weights (exact.h): a work-group of 256 lanes owns R rows.  Per chunk of CB blocks every lane holds 8
+// 16-B pieces of the XL stream (piece l of a row's group: half l & 1 of block l >> 1; 64 consecutive lanes read 8
+// rows x 128 B = 1 KB contiguous), computes their integer dots with the activation's plain Q8_0 blocks in LDS, adds
+// the two halves of a block (integers: exact) and stores p_b = (float)dot_b * f16(w.d_b) -- one rounded multiply,
+// as the reference's -- into s_p; then lane r of wave 0 runs row r's chain sum = fmaf(p_b, x.d_b, sum) over the
+// chunk's blocks in order (ops.cpp:806-824) while the other waves compute the next chunk's products into the other
+// half of s_p.  The chunk after that is already in flight.
+// s_p [2][R][LD]: LD = CB + 4, so the rows of a wave's store (4 consecutive floats each) and the float4s the chain
+// lanes read start 4 banks (R 8: LD = 132) or 20 banks (R 64: LD = 20) apart: no conflicts on 32 or 64 banks.
+template <int R>
+struct Xq8 {
+  static_assert(R == 8 || R == 64, "rows per work-group");
+  static constexpr int IPL = 8;                 // 16-B pieces per lane and chunk
+  static constexpr int CB = IPL * 256 / (8 * R) * 4;  // blocks per chunk: 128 (R 8), 16 (R 64)
+  static constexpr int LD = CB + 4;
+  static constexpr int SP_BYTES = 2 * R * LD * 4;  // 8448 (R 8), 10240 (R 64)
+  uint4 q[IPL];
+  uint16_t d[IPL];
+};
+template <int R>
+__device__ __forceinline__ void xq8_issue(Xq8<R>& c, __amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rd, int rows,
+                                          int row0, int ng, int c0) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int m = 0; m < Xq8<R>::IPL; m++) {
+    const int i = t + 256 * m, l8 = i & 7, Rr = (i >> 3) & (R - 1), g = (c0 >> 2) + i / (8 * R);
+    const bool in = g < ng && row0 + Rr < rows;  // past the end: out of the descriptor's range (0, no traffic)
+    const int gr = g * rows + row0 + Rr;
+    c.q[m] = buf_ld16(rq, in ? gr * 128 + l8 * 16 : (1 << 30), 0);
+    c.d[m] = buf_ld2(rd, in && !(l8 & 1) ? gr * 8 + (l8 >> 1) * 2 : (1 << 30), 0);
+  }
+}
+template <int R>
+__device__ __forceinline__ void xq8_dots(const Xq8<R>& c, const int4* s_xq, float* s_pb, int ng, int c0) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int m = 0; m < Xq8<R>::IPL; m++) {
+    const int i = t + 256 * m, l8 = i & 7, Rr = (i >> 3) & (R - 1), gl = i / (8 * R), g = (c0 >> 2) + gl;
+    if (g >= ng) break;  // wave-uniform (a wave's 64 pieces are 8 rows of one group)
+    const int4 x = s_xq[(4 * g + (l8 >> 1)) * 2 + (l8 & 1)];
+    int dot = sdot4((int)c.q[m].x, x.x, 0);
+    dot = sdot4((int)c.q[m].y, x.y, dot);
+    dot = sdot4((int)c.q[m].z, x.z, dot);
+    dot = sdot4((int)c.q[m].w, x.w, dot);
+    dot += dpp_i<DPP_QUAD_1032>(dot);  // the block's other half (lane ^ 1)
+    if (!(l8 & 1)) s_pb[Rr * Xq8<R>::LD + 4 * gl + (l8 >> 1)] = __fmul_rn((float)dot, h2f(c.d[m]));
+  }
+}
+// the rows of a work-group: returns row (threadIdx.x)'s sum in the lanes threadIdx.x < R (wave 0).  The first
+// chunk's loads (ca) were issued by the caller; s_p [2][R][LD] floats, 16-B aligned.
+template <int R>
+__device__ __forceinline__ float xq8_rows(Xq8<R>& ca, __amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rd, int rows,
+                                          int row0, int nb, const int4* s_xq, const float* s_xd, float* s_p) {
+  constexpr int CB = Xq8<R>::CB, LD = Xq8<R>::LD;
+  const int t = threadIdx.x, ng = nb >> 2;
+  Xq8<R> cb;
+  float sum = 0.0f;
+  const float4* s_xd4 = reinterpret_cast<const float4*>(s_xd);
+  auto chunk = [&](const Xq8<R>& c, int c0, int buf) {
+    xq8_dots<R>(c, s_xq, s_p + buf * R * LD, ng, c0);
+    __syncthreads();  // (one barrier per chunk: the chain below reads half buf, the next chunk's dots write the other)
+    if (t < R) {
+      const int nbc = min(CB, nb - c0);
+      const float4* p4 = reinterpret_cast<const float4*>(s_p + (buf * R + t) * LD);
+      const float4* d4 = s_xd4 + (c0 >> 2);
+#pragma unroll 4
+      for (int b4 = 0; b4 < nbc / 4; b4++) {
+        const float4 p = p4[b4], d = d4[b4];
+        sum = fmaf(p.x, d.x, sum);
+        sum = fmaf(p.y, d.y, sum);
+        sum = fmaf(p.z, d.z, sum);
+        sum = fmaf(p.w, d.w, sum);
+      }
+    }
+  };
+  for (int c0 = 0; c0 < nb; c0 += 2 * CB) {
+    if (c0 + CB < nb) xq8_issue<R>(cb, rq, rd, rows, row0, ng, c0 + CB);
+    chunk(ca, c0, 0);
+    if (c0 + CB >= nb) break;
+    if (c0 + 2 * CB < nb) xq8_issue<R>(ca, rq, rd, rows, row0, ng, c0 + 2 * CB);
+    chunk(cb, c0 + CB, 1);
+  }
+  return sum;
+}
+
 // XL_K4: PRE / GELU float4 of each operand per thread (n <= 4 XL_K4 T); NCH: chunks of XL_P groups in flight;
 // LPR: lanes per row -- 4 (lane jj holds the reference's accumulators jj and jj + 4) or 8 (PLAIN: one accumulator
 // per lane, twice the waves over the same rows: more of the weight stream in flight for the long down rows)
 // SPR (PRE only, 0: off): SPR rows per work-group with the rows' dots split over all lanes and the chains run
 // after them (as exact_plain_split_kernel): the qkv launch's 64 work-groups of 64 rows left 192 CUs idle in
 // its GEMV phase
-template <int NW, int ROLE, int XL_K4, int NCH, int LPR = 4, int SPR = 0>
+// Q8R (0: a Q4_0 weight): a Q8_0 weight, Q8R rows per work-group (NW 4; xq8_rows above).  The role's prologue is the
+// same code; it leaves the activation as plain Q8_0 blocks (32 int8 + d) instead of the XE entries, and the
+// products' s_p lies over s_a / s_b, dead by then.
+template <int NW, int ROLE, int XL_K4, int NCH, int LPR = 4, int SPR = 0, int Q8R = 0>
 __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __restrict__ wq, const uint2* __restrict__ wd,
                                                              int rows, int nb, XlArgs a) {
   extern __shared__ int4 s_dyn[];
-  int4* s_xe = s_dyn;                                                // [nb][4]
-  float* s_xd = reinterpret_cast<float*>(s_dyn + (size_t)nb * 4);    // [nb]
+  static_assert(Q8R == 0 || (NW == 4 && LPR == 4 && SPR == 0 && ROLE != XL_QUANT), "Q8_0: 256 lanes; PLAIN / PRE / GELU");
+  constexpr int XW = Q8R ? 2 : 4;                                    // int4 of the activation's LDS form per block
+  int4* s_xe = s_dyn;                                                // [nb][4] (Q8_0 weights: [nb][2], q[0..15], q[16..31])
+  float* s_xd = reinterpret_cast<float*>(s_dyn + (size_t)nb * XW);   // [nb]
   float* s_a = s_xd + nb;                                            // PRE: [n] y, then the XBlocks
   float* s_b = s_a + a.n;                                            // PRE: [n] h
   __shared__ float s_scale[2];
@@ -267,7 +366,7 @@ __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __rest
   const int row = (blockIdx.x * NW + wave) * RPW + rl;
   const int ng = nb >> 2;
   // weight stream: issued first, the activation prologue runs while it is in flight
-  const __amdgpu_buffer_rsrc_t rq = buf_rsrc(wq, (uint32_t)((size_t)ng * rows * 64));
+  const __amdgpu_buffer_rsrc_t rq = buf_rsrc(wq, (uint32_t)((size_t)ng * rows * (Q8R ? 128 : 64)));
   const __amdgpu_buffer_rsrc_t rd = buf_rsrc(wd, (uint32_t)((size_t)ng * rows * 8));
   const bool row_ok = row < rows;
   const int voq = row_ok ? (row * 4 + jj) * 16 : (1 << 30), vod = row_ok ? row * 8 : (1 << 30);
@@ -278,12 +377,15 @@ __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __rest
   // PRE / GELU roles 3.2-3.9K cycles; scripts/dev/xl_bench)
   static_assert(SPR == 0 || (ROLE == XL_PRE && NW == 4 && SPR * 8 % 64 == 0 && (SPR & (SPR - 1)) == 0), "SPR: PRE");
   constexpr int SIPL = SPR ? (SPR * 4 * (XL_K4 * T / 32) + T - 1) / T : 1;  // split items per lane (ng <= XL_K4 T / 32)
-  XlChunk ck[SPR ? 1 : NCH];
+  XlChunk ck[SPR || Q8R ? 1 : NCH];
   uint4 sq4[SIPL];
   uint2 sd2[SIPL];
+  Xq8<Q8R ? Q8R : 8> q8c;
   const int srow0 = blockIdx.x * (SPR ? SPR : 1);
   auto issue_w = [&]() {
-    if constexpr (SPR > 0) {  // item i = t + T m: slot jj = i % 4, row R = (i / 4) % SPR, group g = i / (4 SPR)
+    if constexpr (Q8R > 0) {
+      xq8_issue<Q8R>(q8c, rq, rd, rows, blockIdx.x * Q8R, ng, 0);
+    } else if constexpr (SPR > 0) {  // item i = t + T m: slot jj = i % 4, row R = (i / 4) % SPR, group g = i / (4 SPR)
 #pragma unroll
       for (int m = 0; m < SIPL; m++) {
         const int i = t + T * m, jj4 = i & 3, R = (i >> 2) & (SPR - 1), g = i / (4 * SPR);
@@ -318,11 +420,16 @@ __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __rest
       for (int k = 0; k < 4; k++) {
         const int b = b0 + k * T + t;
         if (b < nb) {
-          const uint32_t l4[4] = {lo[k].x, lo[k].y, lo[k].z, lo[k].w}, h4[4] = {hi[k].x, hi[k].y, hi[k].z, hi[k].w};
+          if constexpr (Q8R > 0) {
+            s_xe[b * 2] = make_int4((int)lo[k].x, (int)lo[k].y, (int)lo[k].z, (int)lo[k].w);
+            s_xe[b * 2 + 1] = make_int4((int)hi[k].x, (int)hi[k].y, (int)hi[k].z, (int)hi[k].w);
+          } else {
+            const uint32_t l4[4] = {lo[k].x, lo[k].y, lo[k].z, lo[k].w}, h4[4] = {hi[k].x, hi[k].y, hi[k].z, hi[k].w};
 #pragma unroll
-          for (int j = 0; j < 4; j++)
-            s_xe[b * 4 + j] = make_int4((int)l4[j], (int)h4[j], -8 * sdot4((int)l4[j], 0x01010101, 0),
-                                        -8 * sdot4((int)h4[j], 0x01010101, 0));
+            for (int j = 0; j < 4; j++)
+              s_xe[b * 4 + j] = make_int4((int)l4[j], (int)h4[j], -8 * sdot4((int)l4[j], 0x01010101, 0),
+                                          -8 * sdot4((int)h4[j], 0x01010101, 0));
+          }
           s_xd[b] = d[k];
         }
       }
@@ -430,7 +537,11 @@ __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __rest
         const uint32_t wh = (uint32_t)dpp_i<DPP_ROW_SHL4>((int)w);  // octet lanes 4-7: elements 16-31 of the block
         const int sumh = dpp_i<DPP_ROW_SHL4>(sum);
         const int i4 = k * T + t, b = i4 >> 3, sl = i4 & 7;
-        if (ok && sl < 4) s_xe[b * 4 + sl] = make_int4((int)w, (int)wh, -8 * sum, -8 * sumh);
+        if constexpr (Q8R > 0) {  // the plain block: word sl = q[4 sl .. 4 sl + 3]
+          if (ok) reinterpret_cast<uint32_t*>(s_xe)[b * 8 + sl] = w;
+        } else {
+          if (ok && sl < 4) s_xe[b * 4 + sl] = make_int4((int)w, (int)wh, -8 * sum, -8 * sumh);
+        }
         if (ok && sl == 0) s_xd[b] = h2f(f2h_ggml(dd));
       }
     }
@@ -438,6 +549,20 @@ __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __rest
   __syncthreads();
 
   XL_MARK(5);
+  if constexpr (Q8R > 0) {  // ---- Q8_0 rows: the products by all lanes, the chains by wave 0 ----
+    const float r = xq8_rows<Q8R>(q8c, rq, rd, rows, blockIdx.x * Q8R, nb, s_xe, s_xd, s_a);
+    XL_MARK(6);
+    if constexpr (ROLE == XL_GELU) {
+      static_assert(Q8R == 64, "GELU: 32 gate + 32 up rows per work-group");
+      if (t < 64) s_rows[t] = r;
+      __syncthreads();
+      if (t < 32) xl_gelu_store(s_rows, a, t);
+    } else {
+      const int orow = blockIdx.x * Q8R + t;
+      if (t < Q8R && orow < rows) a.out[orow] = r;
+    }
+    return;
+  }
   if constexpr (SPR > 0) {  // ---- split rows: every (row, block, slot) dot by all lanes, then the chains ----
     constexpr int NBMAX = XL_K4 * T / 8;  // blocks per row: n <= 4 XL_K4 T
     __shared__ __attribute__((aligned(16))) float s_p[SPR * 8 * (NBMAX + 4)];
@@ -514,11 +639,7 @@ __global__ __launch_bounds__(NW * 64) void exact_gemv_kernel(const uint4* __rest
     if (jj == 0) s_rows[wave * 16 + rl] = r;
     __syncthreads();
     // rows [64 u, 64 u + 32) gate, [64 u + 32, 64 u + 64) up of units 32 u .. 32 u + 31 (model.cpp:892-899)
-    if (t < 32) {
-      const float gv = gelu_mul1<true>(s_rows[t], s_rows[32 + t]);
-      a.hid[blockIdx.x * 32 + t] = gv;
-      q8_block_store(gv, true, a.hq + blockIdx.x, t);
-    }
+    if (t < 32) xl_gelu_store(s_rows, a, t);
   } else {
     if (jl == 0 && row_ok) a.out[row] = r;
   }
@@ -683,6 +804,40 @@ __global__ void xl_repack_kernel(const uint4* __restrict__ q0, const uint16_t* _
   const uint32_t* qb = reinterpret_cast<const uint32_t*>(q + (size_t)sr * nb + 4 * g);
   oq[i] = make_uint4(qb[jj], qb[4 + jj], qb[8 + jj], qb[12 + jj]);
   if (jj == 0) {
+    const uint16_t* dr = d + (size_t)sr * nb + 4 * g;
+    od[(size_t)g * rows + R] = make_uint2((uint32_t)dr[0] | ((uint32_t)dr[1] << 16), (uint32_t)dr[2] | ((uint32_t)dr[3] << 16));
+  }
+}
+
+// repack: standard device Q8_0 ([rows][nb][32 B] + d [rows][nb]) -> XL (qs [g][row] 128 B: a group's four blocks are
+// contiguous in the source row too; thread (g, R, l8) moves 16 B)
+__global__ void xl_repack_q8_kernel(const uint4* __restrict__ q0, const uint16_t* __restrict__ d0, int r0,
+                                    const uint4* __restrict__ q1, const uint16_t* __restrict__ d1, int r1,
+                                    const uint4* __restrict__ q2, const uint16_t* __restrict__ d2, bool gelu32, int rows,
+                                    int nb, uint4* __restrict__ oq, uint2* __restrict__ od) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  // (g, R, l8)
+  const int ng = nb / 4;
+  if (i >= (size_t)ng * rows * 8) return;
+  const int l8 = (int)(i & 7);
+  const int R = (int)((i >> 3) % rows);
+  const int g = (int)((i >> 3) / rows);
+  const uint4* q;
+  const uint16_t* d;
+  int sr;
+  if (gelu32) {  // gate 32 k.., up 32 k..
+    const int u = R / 64, k = R % 64;
+    q = k < 32 ? q0 : q1;
+    d = k < 32 ? d0 : d1;
+    sr = 32 * u + (k & 31);
+  } else if (R < r0) {
+    q = q0; d = d0; sr = R;
+  } else if (R < r0 + r1) {
+    q = q1; d = d1; sr = R - r0;
+  } else {
+    q = q2; d = d2; sr = R - r0 - r1;
+  }
+  oq[i] = q[((size_t)sr * nb + 4 * g) * 2 + l8];
+  if (l8 == 0) {
     const uint16_t* dr = d + (size_t)sr * nb + 4 * g;
     od[(size_t)g * rows + R] = make_uint2((uint32_t)dr[0] | ((uint32_t)dr[1] << 16), (uint32_t)dr[2] | ((uint32_t)dr[3] << 16));
   }
@@ -1615,6 +1770,35 @@ __global__ __launch_bounds__(256) void xp_norm_kernel(XpNormArgs a) {
 // fmaf): 17 instead of 25 VALU issues per (row, token, block).  -DXG_NO_PK: the scalar form.
 constexpr int XG_R = 64, XG_T = 64, XG_CB = 16;
 typedef float xg_f2 __attribute__((ext_vector_type(2)));
+// the tile's results, thread (rg, tg) = (t % 16, t / 16) holding rows RM rg + RS i and tokens 4 tg + j (any weight
+// type): out [T][ldo], or (hq) the GELU epilogue through s_r [64 rows][65] (LDS no longer read by the tile's loop)
+template <int RM, int RS>
+__device__ __forceinline__ void xg_finish(const float (&r)[4][4], float* s_r, int t, int rg, int tg, int row0, int tok0,
+                                          int rows, int T, float* __restrict__ out, int ldo, XBlock* __restrict__ hq) {
+  if (!hq) {
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int row = row0 + RM * rg + RS * i, tok = tok0 + 4 * tg + j;
+        if (row < rows && tok < T) out[(size_t)tok * ldo + row] = r[i][j];
+      }
+    return;
+  }
+  // GELU epilogue (gelu32 rows: 32 gate rows, then their 32 up rows): GELU(gate) * up of the work-group's 32
+  // hidden units for each token (model.cpp:892-899), quantized as one Q8_0 block per token (ops.cpp:116-139)
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) s_r[(RM * rg + RS * i) * 65 + 4 * tg + j] = r[i][j];
+  __syncthreads();
+  const int u = t & 31, nh = rows / 64;
+  for (int tk = t >> 5; tk < XG_T; tk += 8) {
+    const int tok = tok0 + tk;
+    const float v = gelu_mul1<true>(s_r[u * 65 + tk], s_r[(32 + u) * 65 + tk]);
+    q8_block_store(v, tok < T, hq + (size_t)min(tok, T - 1) * nh + blockIdx.x, u);
+  }
+}
 __global__ __launch_bounds__(256, 2) void xp_gemm_kernel(const uint4* __restrict__ wq, const uint2* __restrict__ wd,
                                                          int rows, int nb, const XBlock* __restrict__ x, int T,
                                                          float* __restrict__ out, int ldo, XBlock* __restrict__ hq) {
@@ -1720,30 +1904,91 @@ __global__ __launch_bounds__(256, 2) void xp_gemm_kernel(const uint4* __restrict
       const xg_f2* v = acc[i][j];  // v[s].x = a_s, v[s].y = a_(s + 4)
       r[i][j] = ((v[0].x + v[0].y) + (v[2].x + v[2].y)) + ((v[1].x + v[1].y) + (v[3].x + v[3].y));
     }
-  if (!hq) {
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int row = row0 + 4 * rg + i, tok = tok0 + 4 * tg + j;
-        if (row < rows && tok < T) out[(size_t)tok * ldo + row] = r[i][j];
-      }
-    return;
-  }
-  // GELU epilogue (gelu32 rows: 32 gate rows, then their 32 up rows): GELU(gate) * up of the work-group's 32
-  // hidden units for each token (model.cpp:892-899), quantized as one Q8_0 block per token (ops.cpp:116-139)
-  float* s_r = reinterpret_cast<float*>(&s_x[0][0][0]);  // [64 rows][65]
+  xg_finish<4, 1>(r, reinterpret_cast<float*>(&s_x[0][0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq);
+}
+
+// The same for a Q8_0 weight (exact.h): each (row, token) one chain over the blocks in order, sum = fmaf((float)dot *
+// f16(w.d), f16(x.d), sum) (ops.cpp:806-824) -- the multiply and the fma two roundings, as the reference's.  Thread
+// (rg, tg) owns rows rg + 16 i (16 lanes read 16 consecutive 32-B rows of s_q: whole bank rows) and tokens 4 tg + j.
+constexpr int XQ_CB = 8;
+__global__ __launch_bounds__(256, 2) void xp_gemm_q8_kernel(const uint4* __restrict__ wq, const uint2* __restrict__ wd,
+                                                            int rows, int nb, const XBlock* __restrict__ x, int T,
+                                                            float* __restrict__ out, int ldo, XBlock* __restrict__ hq) {
+  __shared__ __attribute__((aligned(16))) uint4 s_q[2][XQ_CB][64][2];  // [0]: the rows' 32 quants, [1]: the tokens'
+  __shared__ float s_wd[XQ_CB][XG_R];                                  // f16(w.d)
+  __shared__ float s_xd[XQ_CB][XG_T];
+  static_assert(sizeof(s_q) >= 64 * 65 * 4, "the GELU epilogue's staging");
+  const int t = threadIdx.x, rg = t & 15, tg = t >> 4;
+  const int row0 = blockIdx.x * XG_R, tok0 = blockIdx.y * XG_T, ng = nb >> 2;
+  float acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; i++)
 #pragma unroll
-    for (int j = 0; j < 4; j++) s_r[(4 * rg + i) * 65 + 4 * tg + j] = r[i][j];
-  __syncthreads();
-  const int u = t & 31, nh = rows / 64;
-  for (int tk = t >> 5; tk < XG_T; tk += 8) {
-    const int tok = tok0 + tk;
-    const float v = gelu_mul1<true>(s_r[u * 65 + tk], s_r[(32 + u) * 65 + tk]);
-    q8_block_store(v, tok < T, hq + (size_t)min(tok, T - 1) * nh + blockIdx.x, u);
+    for (int j = 0; j < 4; j++) acc[i][j] = 0.0f;
+  for (int c0 = 0; c0 < nb; c0 += XQ_CB) {
+    // weights: XL qs [g][row] 128 B, piece l8 = half l8 & 1 of block l8 >> 1 of the group
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      const int i = t + 256 * m, l8 = i & 7, R = (i >> 3) & 63, gl = i >> 9, g = (c0 >> 2) + gl;
+      const bool in = g < ng && row0 + R < rows;
+      s_q[0][4 * gl + (l8 >> 1)][R][l8 & 1] = in ? wq[((size_t)g * rows + row0 + R) * 8 + l8] : make_uint4(0, 0, 0, 0);
+    }
+    if (t < 128) {
+      const int R = t & 63, gl = t >> 6, g = (c0 >> 2) + gl;
+      const bool in = g < ng && row0 + R < rows;
+      const uint2 dv = in ? wd[(size_t)g * rows + row0 + R] : make_uint2(0, 0);
+      s_wd[4 * gl + 0][R] = h2f((uint16_t)(dv.x & 0xFFFFu));
+      s_wd[4 * gl + 1][R] = h2f((uint16_t)(dv.x >> 16));
+      s_wd[4 * gl + 2][R] = h2f((uint16_t)(dv.y & 0xFFFFu));
+      s_wd[4 * gl + 3][R] = h2f((uint16_t)(dv.y >> 16));
+    }
+    // the tokens' quants and scales
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      const int i = t + 256 * m, half = i & 1, tk = (i >> 1) & 63, bl = i >> 7, b = c0 + bl, tok = tok0 + tk;
+      const bool in = b < nb && tok < T;
+      const XBlock* xb = x + (size_t)(in ? tok : 0) * nb + (in ? b : 0);
+      s_q[1][bl][tk][half] = in ? (half ? *reinterpret_cast<const uint4*>(&xb->hi) : *reinterpret_cast<const uint4*>(&xb->lo))
+                                : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+      const int i = t + 256 * m, tk = i & 63, bl = i >> 6, b = c0 + bl, tok = tok0 + tk;
+      const bool in = b < nb && tok < T;
+      s_xd[bl][tk] = in ? x[(size_t)tok * nb + b].d : 0.0f;
+    }
+    __syncthreads();
+    const int nbc = min(XQ_CB, nb - c0);
+    for (int bl = 0; bl < nbc; bl++) {
+      uint4 xa[4][2];
+      float xd[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        xa[j][0] = s_q[1][bl][4 * tg + j][0];
+        xa[j][1] = s_q[1][bl][4 * tg + j][1];
+        xd[j] = s_xd[bl][4 * tg + j];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const uint4 w0 = s_q[0][bl][rg + 16 * i][0], w1 = s_q[0][bl][rg + 16 * i][1];
+        const float dw = s_wd[bl][rg + 16 * i];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          int dot = sdot4((int)w0.x, (int)xa[j][0].x, 0);
+          dot = sdot4((int)w0.y, (int)xa[j][0].y, dot);
+          dot = sdot4((int)w0.z, (int)xa[j][0].z, dot);
+          dot = sdot4((int)w0.w, (int)xa[j][0].w, dot);
+          dot = sdot4((int)w1.x, (int)xa[j][1].x, dot);
+          dot = sdot4((int)w1.y, (int)xa[j][1].y, dot);
+          dot = sdot4((int)w1.z, (int)xa[j][1].z, dot);
+          dot = sdot4((int)w1.w, (int)xa[j][1].w, dot);
+          acc[i][j] = fmaf(__fmul_rn((float)dot, dw), xd[j], acc[i][j]);
+        }
+      }
+    }
+    __syncthreads();  // the chunk's LDS is refilled next
   }
+  xg_finish<1, 16>(acc, reinterpret_cast<float*>(&s_q[0][0][0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq);
 }
 
 }  // namespace
@@ -1770,7 +2015,7 @@ void exact_selftest_f16(unsigned long long* host_out3) {
 }
 
 bool xl_supported(const DevWeight& w) {
-  return w.type == T_Q4_0 && !w.slab && w.cols % 128 == 0 && w.rows > 0;
+  return (w.type == T_Q4_0 || w.type == T_Q8_0) && !w.slab && w.cols % 128 == 0 && w.rows > 0;
 }
 
 XlWeight make_xl_weight(const XlSrc& src, hipStream_t s) {
@@ -1780,6 +2025,7 @@ XlWeight make_xl_weight(const XlSrc& src, hipStream_t s) {
   size_t bytes = 0;
   for (int k = 0; k < src.n; k++) {
     if (!xl_supported(*src.w[k]) || src.w[k]->cols != cols) throw std::runtime_error("xl: unsupported weight");
+    if (src.w[k]->type != src.w[0]->type) throw std::runtime_error("xl: sources of different types");
     rows += src.w[k]->rows;
     bytes += src.w[k]->bytes;
   }
@@ -1789,15 +2035,22 @@ XlWeight make_xl_weight(const XlSrc& src, hipStream_t s) {
   x.rows = rows;
   x.nb = cols / 32;
   x.bytes = bytes;
-  const size_t ng = (size_t)x.nb / 4;
-  x.qs = static_cast<uint4*>(dev_alloc(ng * rows * 64 + 256));
+  x.type = src.w[0]->type;
+  const bool q8 = x.type == T_Q8_0;
+  const size_t ng = (size_t)x.nb / 4, gbytes = q8 ? 128 : 64;  // a row's bytes per group
+  if (ng * rows * gbytes >= ((size_t)1 << 31)) throw std::runtime_error("xl: weight exceeds the 32-bit load offsets");
+  x.qs = static_cast<uint4*>(dev_alloc(ng * rows * gbytes + 256));
   x.d = static_cast<uint2*>(dev_alloc(ng * rows * 8 + 256));
   auto Q = [&](int k) { return k < src.n ? reinterpret_cast<const uint4*>(src.w[k]->qs) : nullptr; };
   auto D = [&](int k) { return k < src.n ? src.w[k]->d : nullptr; };
   auto R = [&](int k) { return k < src.n ? src.w[k]->rows : 0; };
-  const size_t n = ng * rows * 4;
-  hipLaunchKernelGGL(xl_repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Q(0), D(0), R(0), Q(1), D(1),
-                     R(1), Q(2), D(2), src.gelu32, rows, x.nb, x.qs, x.d);
+  const size_t n = ng * rows * (gbytes / 16);
+  if (q8)
+    hipLaunchKernelGGL(xl_repack_q8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Q(0), D(0), R(0), Q(1),
+                       D(1), R(1), Q(2), D(2), src.gelu32, rows, x.nb, x.qs, x.d);
+  else
+    hipLaunchKernelGGL(xl_repack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Q(0), D(0), R(0), Q(1), D(1),
+                       R(1), Q(2), D(2), src.gelu32, rows, x.nb, x.qs, x.d);
   LLMI_HIP(hipGetLastError());
   return x;
 }
@@ -1825,12 +2078,47 @@ void launch_exact_attn(const XAttnArgs& a, hipStream_t s) {
   LLMI_HIP(hipGetLastError());
 }
 
+// Q8_0 weights: 256 lanes per work-group, 8 rows (PLAIN, PRE) or the GELU role's 64.  Dynamic LDS: the activation's
+// blocks, 36 B per block, then the larger of the prologue's operands (PRE / GELU: 2 n floats) and the products'
+// s_p (8448 B for 8 rows, 10240 B for 64), which lies over them.  By input-width class (static LDS -- the scales,
+// the GELU rows and the speculative chain's words -- is under 2 KB):
+//   n <= 1536 (XL_K4 2): 1728 + max(12288, 10240) = 14016 B
+//   n <= 3072 (XL_K4 3): 3456 + 24576            = 28032 B
+//   n <= 6144 (XL_K4 6): 6912 + 49152            = 56064 B  (of the 64 KB a work-group may hold)
+// PLAIN takes any length the LDS holds: 36 B per block + 8448 (the 27B down rows: 672 blocks, 32640 B).
+static void launch_exact_gemv_q8(const XlWeight& w, const XlArgs& a, int role, hipStream_t s) {
+  const bool pre = role == XL_PRE || role == XL_GELU;
+  const size_t sp = role == XL_GELU ? Xq8<64>::SP_BYTES : Xq8<8>::SP_BYTES;
+  const size_t lds = (size_t)w.nb * 36 + std::max(pre ? (size_t)2 * a.n * 4 : 0, sp);
+  if (lds > 62 * 1024) throw std::runtime_error("exact gemv: activation exceeds LDS");
+  auto go = [&](auto kern, int rpg) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)(w.rows / rpg)), dim3(256), lds, s, w.qs, w.d, w.rows, w.nb, a);
+  };
+  const bool k2 = a.n <= 12 * 128, k3 = a.n <= 12 * 256;
+  switch (role) {
+    case XL_PLAIN: go(exact_gemv_kernel<4, XL_PLAIN, 1, 1, 4, 0, 8>, 8); break;
+    case XL_PRE:
+      if (k2) go(exact_gemv_kernel<4, XL_PRE, 2, 1, 4, 0, 8>, 8);
+      else if (k3) go(exact_gemv_kernel<4, XL_PRE, 3, 1, 4, 0, 8>, 8);
+      else go(exact_gemv_kernel<4, XL_PRE, 6, 1, 4, 0, 8>, 8);
+      break;
+    case XL_GELU:
+      if (k2) go(exact_gemv_kernel<4, XL_GELU, 2, 1, 4, 0, 64>, 64);
+      else if (k3) go(exact_gemv_kernel<4, XL_GELU, 3, 1, 4, 0, 64>, 64);
+      else go(exact_gemv_kernel<4, XL_GELU, 6, 1, 4, 0, 64>, 64);
+      break;
+    default: throw std::runtime_error("exact gemv: Q8_0 weights take the PLAIN, PRE and GELU roles");
+  }
+  LLMI_HIP(hipGetLastError());
+}
+
 void launch_exact_gemv(const XlWeight& w, const XlArgs& a_in, int role, hipStream_t s) {
   XlArgs a = a_in;
   if (!w.qs || w.nb % 4 || w.rows % 16) throw std::runtime_error("exact gemv: bad weight");
   if (role != XL_PLAIN && a.n != w.nb * 32) throw std::runtime_error("exact gemv: input length != cols");
   if (role == XL_GELU && w.rows % 64) throw std::runtime_error("exact gemv: GELU rows % 64 != 0");
   if ((role == XL_PRE || role == XL_GELU) && a.n > 24 * 256) throw std::runtime_error("exact gemv: n > 6144");
+  if (w.type == T_Q8_0) return launch_exact_gemv_q8(w, a, role, s);
   const size_t xe = (size_t)w.nb * 64 + (size_t)w.nb * 4;
   const size_t lds = xe + (role == XL_PLAIN ? 0 : (size_t)2 * a.n * 4);
   if (lds > 64 * 1024) throw std::runtime_error("exact gemv: activation exceeds LDS");
@@ -1898,7 +2186,8 @@ void launch_exact_gemm(const XlWeight& w, const XBlock* x, int T, float* out, in
   if (!w.qs || w.nb % 4 || w.rows % 16 || T <= 0 || !x || (!out && !hq)) throw std::runtime_error("exact gemm: bad arguments");
   if (hq && w.rows % 64) throw std::runtime_error("exact gemm: GELU rows % 64 != 0");
   const dim3 grid((unsigned)((w.rows + XG_R - 1) / XG_R), (unsigned)((T + XG_T - 1) / XG_T));
-  hipLaunchKernelGGL(xp_gemm_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq);
+  if (w.type == T_Q8_0) hipLaunchKernelGGL(xp_gemm_q8_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq);
+  else hipLaunchKernelGGL(xp_gemm_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq);
   LLMI_HIP(hipGetLastError());
 }
 

@@ -1391,8 +1391,10 @@ void Session::record_layers_fused(hipStream_t s, bool x_q8) {
   dump("result_norm", xn_, E, s);
 }
 
-// Exact mode on the exact-order engine (exact.h): every Gemma-3 layer with Q4_0 q, k, v, o, gate, up and down
-// (the 4B / 1B / 27B Q4_0 files) gets XL copies of its weights; LLMI_EXACT_XL=0 keeps the per-op exact kernels.
+// Exact mode on the exact-order engine (exact.h): every Gemma-3 layer whose q, k, v, o, gate, up and down are each
+// Q4_0 or Q8_0 (the 4B / 1B / 27B Q4_0 files, the 1B Q8_0 file) gets XL copies of its weights -- q/k/v of one type,
+// gate/up of one type, since each pair is one XL weight; tensor-parallel sessions: Q4_0 only.  LLMI_EXACT_XL=0
+// keeps the per-op exact kernels.
 void Session::setup_xl() {
   if (!exact_ || hp_.gemma4 || ple_table_.qs || getenv("LLMI_EXACT_PARTS")) return;
   if (const char* e = getenv("LLMI_EXACT_XL"))
@@ -1404,8 +1406,10 @@ void Session::setup_xl() {
   for (const auto& l : L_) {
     bool ok = l.has_kv && !l.qkv.empty() && !l.gate_up.empty() && (hp_.n_head * l.hd) % 128 == 0 &&
               exact_attn_supported(l.hd, hp_.n_head, hp_.n_head_kv);
-    for (const auto& p : l.qkv) ok = ok && xl_supported(p.w);
-    for (const auto& p : l.gate_up) ok = ok && xl_supported(p.w);
+    for (const auto& p : l.qkv) ok = ok && xl_supported(p.w) && p.w.type == l.qkv[0].w.type;
+    for (const auto& p : l.gate_up) ok = ok && xl_supported(p.w) && p.w.type == l.gate_up[0].w.type;
+    if (tp_ && ok)
+      for (const DevWeight* w : {&l.qkv[0].w, &l.gate_up[0].w, &l.o.w, &l.down.w}) ok = ok && w->type == T_Q4_0;
     int gu_rows = 0;
     for (const auto& p : l.gate_up) gu_rows += p.w.rows;
     ok = ok && xl_supported(l.o.w) && xl_supported(l.down.w) && gu_rows == 2 * F && !l.gu_interleaved &&
@@ -1419,9 +1423,9 @@ void Session::setup_xl() {
       const int nb = gate.cols / 32;
       gate.rows = F;
       up = gate;
-      up.qs = static_cast<uint8_t*>(gate.qs) + (size_t)F * nb * 16;
+      up.qs = static_cast<uint8_t*>(gate.qs) + (size_t)F * nb * (gate.type == T_Q8_0 ? 32 : 16);
       up.d = gate.d + (size_t)F * nb;
-      gate.bytes = up.bytes = gguf_bytes(T_Q4_0, F, gate.cols);
+      gate.bytes = up.bytes = gguf_bytes(gate.type, F, gate.cols);
     } else {
       up = l.gate_up[1].w;
     }
