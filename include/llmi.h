@@ -49,6 +49,8 @@ typedef enum {
 #define LLMI_NO_GRAPH 2u   /* session: launch kernels eagerly instead of one hipGraph per token */
 #define LLMI_TP_PEER 4u    /* session: tensor-parallel rank of tp_size processes (one per GPU) exchanging by
                               one-shot peer push (llmi_session_peer_connect) instead of RCCL */
+#define LLMI_EXACT_KQ 8u   /* session, with LLMI_EXACT only: the exact-order engine also takes K-quant (Q4_K / Q6_K)
+                              layers; opt-in, also set by LLMI_EXACT_KQ=1 in the environment at session creation */
 
 const char* llmi_last_error(void);
 int llmi_version(void);
@@ -109,7 +111,7 @@ typedef struct llmi_tp_group llmi_tp_group;
 
 typedef struct {
   int device;          /* HIP device ordinal */
-  uint32_t flags;      /* LLMI_EXACT | LLMI_NO_GRAPH */
+  uint32_t flags;      /* LLMI_EXACT | LLMI_NO_GRAPH | LLMI_TP_PEER | LLMI_EXACT_KQ */
   int max_ctx;         /* KV-cache capacity in positions (default 4096) */
   int attn_split;      /* fast attention key-range splits: 0 = default (32, the only value) */
   /* Row-sharded tensor parallelism (north star: "weights shard row-wise across
@@ -217,9 +219,15 @@ typedef struct {
   int exact_engine;           /* 1: LLMI_EXACT runs on the exact-order engine (k_exact.hip: the reference's
                                  arithmetic with streamed GEMVs and fused norms; Gemma-3 layers whose projections are
                                  each Q4_0 or Q8_0, q/k/v of one type and gate/up of one type; tensor-parallel
-                                 sessions: Q4_0 only), 0: the per-op exact kernels */
+                                 sessions: Q4_0 only; with LLMI_EXACT_KQ, one device: each of q|k|v, o, gate|up, down
+                                 may instead be Q4_K / Q6_K with columns % 256 == 0 -- q, k, v with at most one change
+                                 of type along them (Q4_K_M's q|k Q4_K, v Q6_K), gate and up both Q4_K (both Q6_K is
+                                 turned away), o and down either; the two families may alternate between launches,
+                                 not inside q|k|v or gate|up), 0: the per-op exact kernels (always with
+                                 LLMI_EXACT_XL=0) */
   int exact_batched_prefill;  /* 1: an exact session runs a prompt's tokens before the last layer by layer, T at a
-                                 time (the reference's chains per (row, token)), then the last as a decode step */
+                                 time (the reference's chains per (row, token)), then the last as a decode step
+                                 (every type combination the engine accepts) */
   int prefill_gemm;           /* the batched prefill's GEMM: 7 f16 MFMA on f16 rows of the dequantized Q8_0 activation
                                  blocks (Q4_0 layers, one device: the default), 5 int8 MFMA on Q8_0 / Q8_K blocks
                                  (LLMI_PREFILL_F16=0, Q8_0 weights, tensor-parallel ranks), 6 f16 for K-quant layers

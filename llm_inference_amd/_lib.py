@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("LLMI_LIB") or os.path.join(HERE, "libllmi.so")
 LLMI_EXACT = 1
 LLMI_NO_GRAPH = 2
 LLMI_TP_PEER = 4
+LLMI_EXACT_KQ = 8  # with LLMI_EXACT: the exact-order engine also takes K-quant layers
 PEER_HANDLE_BYTES = 64
 
 STATUS = {0: "OK", 1: "E_SIZE", 2: "E_TYPE", 3: "E_ARG", 4: "E_HIP", 5: "E_GGUF", 6: "E_NODEV", 7: "E_RANGE"}

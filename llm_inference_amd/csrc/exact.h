@@ -23,6 +23,25 @@
 //   d  [g][row] 8 B   = the four blocks' f16 scales
 // so one wave-instruction of a group reads 8 rows x 8 lanes x 16 B = 1 KB contiguous (lane l of a row: half l & 1
 // of block l >> 1).
+//
+// K-quant weights (LLMI_EXACT_KQ).  The activation is quantize_row_q8_k's (ops.cpp:142-178).  The reference's Q4_K row
+// (ops.cpp:614-700) is one chain of plain adds, sum = sum + t_j over the eight 32-element sub-blocks of every super-block
+// in order, t_j = fmaf((float)a_j, (f16(w.d) x.d) sc_j, -(((f16(w.dmin) x.d) m_j) (float)(bs_2j + bs_2j+1))) with a_j an
+// exact integer dot: every t_j depends on nothing before it.  Its Q6_K row (ops.cpp:702-785) is sum = fmaf((float)part,
+// f16(w.d) x.d, sum) over the two 128-element halves of every super-block, part the half's whole int32 sum of
+// sc * (q - 32) * x (it can exceed 2^24, so it is complete before its one conversion).  All lanes compute the t_j /
+// (float)part, one lane per row runs the chain.
+//
+// XL layout of a K-quant weight [rows][nsb] (cols % 256 == 0), piece (sb, row, l8), l8 < 8:
+//   qs [sb][row][l8] 16 B: Q4_K the q4 bytes 16 l8 .. 16 l8 + 15 (low nibbles: sub-block l8 & ~1, high: l8 | 1; elements
+//                          16 (l8 & 1) ..); Q6_K the ql bytes 16 c .. of half n (l8 = 4 n + c; low nibbles: 16-element
+//                          group 8 n + c, high nibbles: group 8 n + c + 4)
+//   qh [sb][row][l8] 8 B : Q6_K only: the two high bits of the piece's low-nibble (x) and high-nibble (y) quants, quant
+//                          j = 4 k + e at bit 8 e + 2 k (a shift and a mask per word of four quants)
+//   sw [sb][row][l8] 4 B : Q4_K {sc_l8, m_l8 (6 bits each, unpacked), f16 d (even l8) or dmin (odd l8)};
+//                          Q6_K {sc of the low group, sc of the high group (int8), f16 d}
+// so one wave-instruction reads 8 rows x 8 pieces x 16 B = 1 KB contiguous (160 B per Q4_K super-block against the
+// file's 144, 224 B per Q6_K super-block against 210).
 #pragma once
 
 #include "session_kernels.h"
@@ -34,7 +53,10 @@ struct XlWeight {
   uint2* d = nullptr;
   int rows = 0, nb = 0;
   size_t bytes = 0;  // algorithmic (GGUF) bytes
-  uint32_t type = T_Q4_0;  // T_Q4_0 or T_Q8_0: which of the two layouts above qs holds
+  uint32_t type = T_Q4_0;  // T_Q4_0, T_Q8_0, T_Q4_K or T_Q6_K: which of the layouts above qs holds
+  uint2* qh = nullptr;     // K-quant layouts: the Q6_K high bits
+  uint32_t* sw = nullptr;  //                  the scale words
+  XlWeight* tail = nullptr;  // K-quant q|k|v with parts of two types: the rows after this weight's (owned)
 };
 
 // sources of an XL weight: rows [0, n) of each device Q4_0 / Q8_0 weight (row-major blocks; one type for all the
@@ -45,11 +67,14 @@ struct XlSrc {
   int n = 0;
   bool gelu32 = false;
 };
-bool xl_supported(const DevWeight& w);
+bool xl_supported(const DevWeight& w);     // Q4_0 / Q8_0
+bool xl_kq_supported(const DevWeight& w);  // Q4_K / Q6_K in the file's block order, cols % 256 == 0
 XlWeight make_xl_weight(const XlSrc& src, hipStream_t s);
 void free_xl_weight(XlWeight& w);
 
 enum XlRole {
+  // (a K-quant weight: Q8_K for Q8_0 throughout -- PLAIN reads the XBlocks of q8k_block_quad, the prologues of the
+  // other roles end in quantize_row_q8_k; the GELU epilogue is the same)
   XL_PLAIN = 0,  // x = the Q8_0 blocks at xb
   XL_QUANT = 1,  // x = quantize_row_q8_0(y)
   XL_PRE = 2,    // h = resid_in (+ rms(y) * w_post when y); resid_out = h; x = Q8_0(rms(h) * w_next)
@@ -138,11 +163,14 @@ struct XpNormArgs {
   XBlock* xq = nullptr;            // [T][n / 32]
   int n = 0;
   double eps = 0;
+  int q8k = 0;                     // 1: xq = the Q8_K quants (q8k_block_quad's XBlocks) for a K-quant consumer
 };
 void launch_exact_norm_batch(const XpNormArgs& a, int T, hipStream_t s);
 // rows x T tokens of an XL weight on the tokens' Q8_0 blocks x [T][nb]: out [T][ldo] (plain), or (gelu32 weights)
 // GELU(gate) * up of each 32-unit group -> hq [T][rows / 64] Q8_0 blocks
-void launch_exact_gemm(const XlWeight& w, const XBlock* x, int T, float* out, int ldo, XBlock* hq, hipStream_t s);
+// (a K-quant weight reads K-convention XBlocks; hid: the GELU form also / instead writes GELU(gate) * up as f32 [T][rows / 2])
+void launch_exact_gemm(const XlWeight& w, const XBlock* x, int T, float* out, int ldo, XBlock* hq, hipStream_t s,
+                       float* hid = nullptr);
 // self-test (synchronous): over every f32 bit pattern, out[0] = non-NaN inputs whose hardware f16 conversion
 // differs from the reference's f32_to_f16, out[1] = NaN inputs that differ, out[2] = the first non-NaN one
 void exact_selftest_f16(unsigned long long* out3);

@@ -1,7 +1,8 @@
 // k_exact.hip -- the exact-order engine's Q4_0 and Q8_0 GEMVs (exact.h): the
 // reference's operation order (ops.cpp:364-399 mat_vec_mul_q4_0, ops.cpp:806-824 the Q8_0 row, ops.cpp:28-43
 // rms_norm, ops.cpp:116-139 quantize_row_q8_0, model.cpp:843-924 residual /
-// norm / GELU) with the weights streamed like the fast path's layer GEMVs.
+// norm / GELU) with the weights streamed like the fast path's layer GEMVs; and, opt-in, its K-quant GEMVs
+// (ops.cpp:614-785 the Q4_K / Q6_K rows, ops.cpp:142-178 quantize_row_q8_k).
 #include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
@@ -1674,10 +1675,409 @@ __device__ __forceinline__ float xp_deq(uint32_t type, const uint8_t* row, int i
   }
 }
 
+// ---------------------------------------------------------------------------
+// K-quant weights (exact.h): Q4_K / Q6_K rows on the Q8_K activation
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float xk_wave_max_f(float v) {
+  v = fmaxf(v, dpp_f<DPP_QUAD_1032>(v));
+  v = fmaxf(v, dpp_f<DPP_QUAD_2301>(v));
+  v = fmaxf(v, dpp_f<DPP_ROW_MIRROR>(v));
+  v = fmaxf(v, dpp_f<DPP_ROW_HALF_MIRROR>(v));
+  v = fmaxf(v, __shfl_xor(v, 16));
+  return fmaxf(v, __shfl_xor(v, 32));
+}
+// quantize_row_q8_k (ops.cpp:142-178, as quantize_q8_k_kernel / q8k_block_quad) of the super-block held by a wave,
+// lane l the elements 4 l .. 4 l + 3: max = the signed value of the first element with the largest |x|, iscale =
+// -127 / max, q = nearest_int(iscale x) clamped, d = 1 / iscale; an all-zero super-block stays 0.  Returns the lane's
+// four quants as a word; d in every lane; bs16 = the sum of the lane's 16-element group (its DPP quad).  Every lane
+// of the wave must execute it.
+__device__ __forceinline__ uint32_t xk_q8k_wave(const float4 x, float& d, int& bs16) {
+  const float ax = xk_wave_max_f(fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w))));
+  const int e0 = (int)(threadIdx.x & 63) * 4;
+  int key = 0x7FFFFFFF;
+  if (fabsf(x.w) == ax) key = ((e0 + 3) << 1) | (x.w < 0.0f ? 1 : 0);
+  if (fabsf(x.z) == ax) key = ((e0 + 2) << 1) | (x.z < 0.0f ? 1 : 0);
+  if (fabsf(x.y) == ax) key = ((e0 + 1) << 1) | (x.y < 0.0f ? 1 : 0);
+  if (fabsf(x.x) == ax) key = (e0 << 1) | (x.x < 0.0f ? 1 : 0);
+  key = xa_wave_min(key);
+  uint32_t w = 0;
+  int s = 0;
+  d = 0.0f;
+  if (ax != 0.0f) {  // ops.cpp:158-163
+    const float iscale = -127.f / ((key & 1) ? -ax : ax);
+    d = 1.0f / iscale;
+    const float v[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      int q = nearest_int_fma(iscale, v[e]);
+      q = q < -128 ? -128 : (q > 127 ? 127 : q);
+      s += q;
+      w |= (uint32_t)(q & 0xFF) << (8 * e);
+    }
+  }
+  s += dpp_i<DPP_QUAD_1032>(s);
+  bs16 = s + dpp_i<DPP_QUAD_2301>(s);
+  return w;
+}
+
+// The activation of a K-quant launch in LDS: s_x [n / 16] the quants of each 16-element group (an int4), s_bs
+// [n / 16] the groups' sums (the reference's bsums), s_xd [n / 256] the super-blocks' d.
+struct XkAct {
+  int4* x;
+  int* bs;
+  float* xd;
+};
+// float4 i of the vector (its wave holds super-block i / 64 whole): quantize and store
+__device__ __forceinline__ void xk_q8k_store(const XkAct& s, int i4, const float4 x, bool ok) {
+  float d;
+  int bs16;
+  const uint32_t w = xk_q8k_wave(x, d, bs16);
+  if (ok) {
+    reinterpret_cast<uint32_t*>(s.x)[i4] = w;
+    if ((i4 & 3) == 0) s.bs[i4 >> 2] = bs16;
+    if ((i4 & 63) == 0) s.xd[i4 >> 6] = d;
+  }
+}
+
+// One part of a K-quant XL weight (exact.h): q the 16-B pieces, h the Q6_K high bits, s the scale words
+struct XkPart {
+  const uint4* q;
+  const uint2* h;
+  const uint32_t* s;
+  int rows;
+  int q6;  // 0: Q4_K, 1: Q6_K
+};
+
+// A work-group of 256 lanes owns R rows.  Per chunk of CS super-blocks every lane holds 8 16-B pieces of the XL
+// stream (piece l8 of a row's super-block; 64 consecutive lanes read 8 rows x 128 B = 1 KB contiguous) with their
+// scale words (and, Q6_K, the pieces' 8 B of high bits).
+//   Q4_K (the per-op gemv_q4_k_exact is the pinned form): piece l8 holds q4 bytes 16 l8 .. 16 l8 + 15: the low
+//   nibbles are elements 16 h .. 16 h + 15 of sub-block 2 p, the high nibbles those of sub-block 2 p + 1 (p = l8 >> 1,
+//   h = l8 & 1).  The two halves' integer dots are added across the lane pair (exact), then lane l8 finishes
+//   sub-block l8: t = fmaf((float)a, d sc, -((dmin m) (float)(bs0 + bs1))), d = f16(w.d) x.d, dmin likewise --
+//   every multiply rounded once, nothing depending on an earlier sub-block -- into s_p [row][8 per super-block];
+//   the chain is sum = sum + t over the sub-blocks in order.
+//   Q6_K (gemv_q6_k_exact): piece l8 holds ql bytes 16 c .. 16 c + 15 of half n (n = l8 >> 2, c = l8 & 3): the low
+//   nibbles with their two high bits are the 16-element group 8 n + c, the high nibbles group 8 n + c + 4; each
+//   group's dot of the 6-bit values with the activation, minus 32 times the group's sum (q - 32), times the group's
+//   int8 scale, all in int32 and summed over the half's four lanes: part, complete before its one conversion.
+//   s_p [row][4 per super-block] = {(float)part_0, (float)part_1, d}; the chain is sum = fmaf(part, d, sum), twice.
+// Lane r < R of wave 0 runs row r's chain over a chunk while the other waves fill the other half of s_p.
+// Row strides LD = 8 mod 64 floats: the 8 rows of a wave's store and the chain lanes' float4 reads on distinct banks.
+template <int R, bool Q6>
+struct Xk {
+  static constexpr int IPL = 8;
+  static constexpr int CS = IPL * 256 / (8 * R);  // super-blocks per chunk: 32 (R 8), 4 (R 64)
+  static constexpr int VPS = Q6 ? 4 : 8;          // floats of s_p per super-block
+  static constexpr int LD = CS * VPS + 8;         // Q4_K: 264 (R 8), 40 (R 64); Q6_K: 136 (R 8)
+  static constexpr int SP_BYTES = 2 * R * LD * 4;
+  uint4 q[IPL];
+  uint2 h[Q6 ? IPL : 1];
+  uint32_t s[IPL];
+};
+template <int R, bool Q6>
+__device__ __forceinline__ void xk_issue(Xk<R, Q6>& c, __amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rh,
+                                         __amdgpu_buffer_rsrc_t rs, int rows, int row0, int nsb, int c0) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    const int i = t + 256 * m, l8 = i & 7, Rr = (i >> 3) & (R - 1), sb = c0 + i / (8 * R);
+    const bool in = sb < nsb && row0 + Rr < rows;  // past the end: out of the descriptor's range (0, no traffic)
+    const int pc = (sb * rows + row0 + Rr) * 8 + l8;
+    c.q[m] = buf_ld16(rq, in ? pc * 16 : (1 << 30), 0);
+    c.s[m] = __builtin_amdgcn_raw_buffer_load_b32(rs, in ? pc * 4 : (1 << 30), 0, BUF_NT);
+    if constexpr (Q6) {
+      typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
+      const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rh, in ? pc * 8 : (1 << 30), 0, BUF_NT);
+      c.h[m] = make_uint2(v.x, v.y);
+    }
+  }
+}
+// one piece of a Q4_K row: sub-block l8's t in every lane
+__device__ __forceinline__ float xk_q4k_piece(const uint4 q, uint32_t sw, int l8, int sb, const XkAct& s) {
+  const int h = l8 & 1;
+  const int4 xl = s.x[16 * sb + 2 * (l8 & 6) + h], xh = s.x[16 * sb + 2 * (l8 & 6) + 2 + h];
+  int al = sdot4((int)(q.x & 0x0F0F0F0Fu), xl.x, 0);
+  al = sdot4((int)(q.y & 0x0F0F0F0Fu), xl.y, al);
+  al = sdot4((int)(q.z & 0x0F0F0F0Fu), xl.z, al);
+  al = sdot4((int)(q.w & 0x0F0F0F0Fu), xl.w, al);
+  int ah = sdot4((int)((q.x >> 4) & 0x0F0F0F0Fu), xh.x, 0);
+  ah = sdot4((int)((q.y >> 4) & 0x0F0F0F0Fu), xh.y, ah);
+  ah = sdot4((int)((q.z >> 4) & 0x0F0F0F0Fu), xh.z, ah);
+  ah = sdot4((int)((q.w >> 4) & 0x0F0F0F0Fu), xh.w, ah);
+  al += dpp_i<DPP_QUAD_1032>(al);  // the sub-block's other half (lane ^ 1)
+  ah += dpp_i<DPP_QUAD_1032>(ah);
+  const uint32_t so = (uint32_t)dpp_i<DPP_QUAD_1032>((int)sw);  // even lanes carry f16 d, odd lanes f16 dmin
+  const float xd = s.xd[sb];
+  const float d = __fmul_rn(h2f((uint16_t)((h ? so : sw) >> 16)), xd);
+  const float mn = __fmul_rn(h2f((uint16_t)((h ? sw : so) >> 16)), xd);
+  const float d1 = __fmul_rn(d, (float)(sw & 0xFFu)), m1 = __fmul_rn(mn, (float)((sw >> 8) & 0xFFu));
+  const int2 bs = reinterpret_cast<const int2*>(s.bs)[8 * sb + l8];
+  return fmaf((float)(h ? ah : al), d1, -__fmul_rn(m1, (float)(bs.x + bs.y)));
+}
+// one piece of a Q6_K row: its half's part (the four lanes c summed) in every lane of the quad
+__device__ __forceinline__ int xk_q6k_piece(const uint4 q, const uint2 hb, uint32_t sw, int l8, int sb, const XkAct& s) {
+  const int g = 16 * sb + 8 * (l8 >> 2) + (l8 & 3);
+  const int4 xl = s.x[g], xh = s.x[g + 4];
+  const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
+  const int xl4[4] = {xl.x, xl.y, xl.z, xl.w}, xh4[4] = {xh.x, xh.y, xh.z, xh.w};
+  int dl = 0, dh = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    dl = sdot4((int)((w4[k] & 0x0F0F0F0Fu) | (((hb.x >> (2 * k)) & 0x03030303u) << 4)), xl4[k], dl);
+    dh = sdot4((int)(((w4[k] >> 4) & 0x0F0F0F0Fu) | (((hb.y >> (2 * k)) & 0x03030303u) << 4)), xh4[k], dh);
+  }
+  const int scl = (int)(int8_t)(sw & 0xFFu), sch = (int)(int8_t)((sw >> 8) & 0xFFu);
+  int part = scl * (dl - 32 * s.bs[g]) + sch * (dh - 32 * s.bs[g + 4]);
+  part += dpp_i<DPP_QUAD_1032>(part);
+  return part + dpp_i<DPP_QUAD_2301>(part);
+}
+template <int R, bool Q6>
+__device__ __forceinline__ void xk_dots(const Xk<R, Q6>& c, const XkAct& s, float* s_pb, int nsb, int c0) {
+  const int t = threadIdx.x;
+  constexpr int LD = Xk<R, Q6>::LD;
+#pragma unroll
+  for (int m = 0; m < 8; m++) {
+    const int i = t + 256 * m, l8 = i & 7, Rr = (i >> 3) & (R - 1), sl = i / (8 * R), sb = c0 + sl;
+    if (sb >= nsb) break;  // wave-uniform (a wave's 64 pieces are 8 rows of one super-block)
+    if constexpr (Q6) {
+      const int part = xk_q6k_piece(c.q[m], c.h[m], c.s[m], l8, sb, s);
+      if ((l8 & 3) == 0) s_pb[Rr * LD + 4 * sl + (l8 >> 2)] = (float)part;
+      if (l8 == 1) s_pb[Rr * LD + 4 * sl + 2] = __fmul_rn(h2f((uint16_t)(c.s[m] >> 16)), s.xd[sb]);
+    } else {
+      s_pb[Rr * LD + 8 * sl + l8] = xk_q4k_piece(c.q[m], c.s[m], l8, sb, s);
+    }
+  }
+}
+// the rows of a work-group: row (threadIdx.x)'s sum in the lanes threadIdx.x < R (wave 0); s_p [2][R][LD] floats
+template <int R, bool Q6>
+__device__ __forceinline__ float xk_rows(const XkPart& w, int row0, int nsb, const XkAct& s, float* s_p) {
+  constexpr int CS = Xk<R, Q6>::CS, LD = Xk<R, Q6>::LD;
+  const int t = threadIdx.x;
+  const uint32_t pieces = (uint32_t)nsb * (uint32_t)w.rows * 8u;
+  const __amdgpu_buffer_rsrc_t rq = buf_rsrc(w.q, pieces * 16u), rh = buf_rsrc(w.h, Q6 ? pieces * 8u : 0u),
+                               rs = buf_rsrc(w.s, pieces * 4u);
+  Xk<R, Q6> ca, cb;
+  float sum = 0.0f;
+  xk_issue<R, Q6>(ca, rq, rh, rs, w.rows, row0, nsb, 0);
+  auto chunk = [&](const Xk<R, Q6>& c, int c0, int buf) {
+    xk_dots<R, Q6>(c, s, s_p + buf * R * LD, nsb, c0);
+    __syncthreads();  // (one barrier per chunk: the chain below reads half buf, the next chunk's dots write the other)
+    if (t < R) {
+      const int ns = min(CS, nsb - c0);
+      const float4* p4 = reinterpret_cast<const float4*>(s_p + (buf * R + t) * LD);
+      if constexpr (Q6) {
+#pragma unroll 4
+        for (int k = 0; k < ns; k++) {
+          const float4 p = p4[k];
+          sum = fmaf(p.x, p.z, sum);
+          sum = fmaf(p.y, p.z, sum);
+        }
+      } else {
+#pragma unroll 4
+        for (int k = 0; k < 2 * ns; k++) {
+          const float4 p = p4[k];
+          sum = __fadd_rn(sum, p.x);
+          sum = __fadd_rn(sum, p.y);
+          sum = __fadd_rn(sum, p.z);
+          sum = __fadd_rn(sum, p.w);
+        }
+      }
+    }
+  };
+  for (int c0 = 0; c0 < nsb; c0 += 2 * CS) {
+    if (c0 + CS < nsb) xk_issue<R, Q6>(cb, rq, rh, rs, w.rows, row0, nsb, c0 + CS);
+    chunk(ca, c0, 0);
+    if (c0 + CS >= nsb) break;
+    if (c0 + 2 * CS < nsb) xk_issue<R, Q6>(ca, rq, rh, rs, w.rows, row0, nsb, c0 + 2 * CS);
+    chunk(cb, c0 + CS, 1);
+  }
+  return sum;
+}
+
+// The K-quant form of exact_gemv_kernel: the same roles, the activation as Q8_K (XL_PLAIN: the XBlocks of
+// q8k_block_quad -- the Q8_K quants, d = the super-block's d; XL_QUANT: quantize_row_q8_k(y); XL_PRE / XL_GELU: the
+// residual step and the two norms as exact_gemv_kernel's, then quantize_row_q8_k), R rows per work-group (8, or the
+// GELU role's 64).  Rows [0, pa.rows) are part pa, the rest part pb (q|k Q4_K, v Q6_K): a work-group's rows lie in
+// one part, its row body picked by a uniform branch.  BODY: 1 Q4_K rows only, 3 either.
+template <int ROLE, int XL_K4, int R, int BODY>
+__global__ __launch_bounds__(256) void exact_gemv_kq_kernel(XkPart pa, XkPart pb, int nsb, XlArgs a) {
+  extern __shared__ int4 s_dyn[];
+  constexpr int NW = 4, T = 256;
+  const int n = nsb * 256, n4 = n >> 2;
+  XkAct act;
+  act.x = s_dyn;                                           // [n / 16]
+  act.bs = reinterpret_cast<int*>(s_dyn + n / 16);         // [n / 16]
+  act.xd = reinterpret_cast<float*>(act.bs + n / 16);      // [nsb], padded to 16 B
+  float* s_a = act.xd + ((nsb + 3) & ~3);                  // PRE / GELU: [n] y; then the rows' s_p
+  float* s_b = s_a + n;                                    // PRE / GELU: [n] h
+  __shared__ float s_scale[2];
+  __shared__ float s_rows[64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if constexpr (ROLE == XL_PLAIN) {
+    const uint4* xg = reinterpret_cast<const uint4*>(a.xb);  // 3 uint4 per XBlock
+    for (int b = t; b < n / 32; b += T) {
+      const uint4 lo = xg[3 * b], hi = xg[3 * b + 1];
+      act.x[2 * b] = make_int4((int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w);
+      act.x[2 * b + 1] = make_int4((int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w);
+      act.bs[2 * b] = sdot4((int)lo.x, 0x01010101, sdot4((int)lo.y, 0x01010101, sdot4((int)lo.z, 0x01010101, sdot4((int)lo.w, 0x01010101, 0))));
+      act.bs[2 * b + 1] = sdot4((int)hi.x, 0x01010101, sdot4((int)hi.y, 0x01010101, sdot4((int)hi.z, 0x01010101, sdot4((int)hi.w, 0x01010101, 0))));
+      if ((b & 7) == 0) act.xd[b >> 3] = __uint_as_float(xg[3 * b + 2].x);
+    }
+  } else if constexpr (ROLE == XL_QUANT) {
+    // a wave per super-block, four super-blocks' loads in flight per wave
+    const float4* y4 = reinterpret_cast<const float4*>(a.y);
+    for (int sb0 = 0; sb0 < nsb; sb0 += 4 * NW) {
+      float4 v[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = y4[min(sb0 + NW * k + wave, nsb - 1) * 64 + lane];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int sb = sb0 + NW * k + wave;  // wave-uniform
+        if (sb < nsb) xk_q8k_store(act, sb * 64 + lane, v[k], true);
+      }
+    }
+  } else {
+    // thread t owns float4 i = t + k T (k < XL_K4) of every operand (exact_gemv_kernel's PRE prologue)
+    float4* s_a4 = reinterpret_cast<float4*>(s_a);
+    float4* s_b4 = reinterpret_cast<float4*>(s_b);
+    const float4* y4 = reinterpret_cast<const float4*>(a.y);
+    const float4* r4 = reinterpret_cast<const float4*>(a.resid_in);
+    const float4* wp4 = reinterpret_cast<const float4*>(a.w_post);
+    const float4* wn4 = reinterpret_cast<const float4*>(a.w_next);
+    float4 yv[XL_K4], hv[XL_K4], wv[XL_K4], nv[XL_K4];
+#pragma unroll
+    for (int k = 0; k < XL_K4; k++) {
+      const int i = min(k * T + t, n4 - 1);
+      hv[k] = r4[i];
+      if (a.y) {
+        yv[k] = y4[i];
+        wv[k] = wp4[i];
+      }
+      nv[k] = wn4[i];
+    }
+    auto own = [&](int k) { return k * T + t < n4; };
+    if (a.y) {
+#pragma unroll
+      for (int k = 0; k < XL_K4; k++)
+        if (own(k)) s_a4[k * T + t] = yv[k];
+      __syncthreads();
+      const float sc1 = xl_rms_scale(xl_sumsq<NW>(s_a, n, &s_scale[0]), n, a.eps);
+#pragma unroll
+      for (int k = 0; k < XL_K4; k++) {  // model.cpp:843-858: the post norm, then the residual add
+        hv[k].x = hv[k].x + (sc1 * yv[k].x) * wv[k].x;
+        hv[k].y = hv[k].y + (sc1 * yv[k].y) * wv[k].y;
+        hv[k].z = hv[k].z + (sc1 * yv[k].z) * wv[k].z;
+        hv[k].w = hv[k].w + (sc1 * yv[k].w) * wv[k].w;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < XL_K4; k++)
+      if (own(k)) {
+        s_b4[k * T + t] = hv[k];
+        if (blockIdx.x == 0 && (a.y || a.resid_out != a.resid_in))
+          reinterpret_cast<float4*>(a.resid_out)[k * T + t] = hv[k];
+      }
+    __syncthreads();
+    const float sc2 = xl_rms_scale(xl_sumsq<NW>(s_b, n, &s_scale[1]), n, a.eps);
+    // run_norm: (scale * x) * w (model.cpp:352-357), then quantize_row_q8_k straight from the registers: a wave's 64
+    // float4 of a k round are one super-block (n4 and T are multiples of 64)
+#pragma unroll
+    for (int k = 0; k < XL_K4; k++) {
+      const bool ok = own(k);  // (whole waves)
+      const float4 x = make_float4((sc2 * hv[k].x) * nv[k].x, (sc2 * hv[k].y) * nv[k].y, (sc2 * hv[k].z) * nv[k].z,
+                                   (sc2 * hv[k].w) * nv[k].w);
+      if (ok && blockIdx.x == 0 && a.xn_out) reinterpret_cast<float4*>(a.xn_out)[k * T + t] = x;
+      xk_q8k_store(act, k * T + t, x, ok);
+    }
+  }
+  __syncthreads();
+  // ---- the rows: the per-piece values by all lanes, the chains by wave 0 ----
+  const int rowg = blockIdx.x * R;  // (pa.rows % R == 0: a work-group's rows lie in one part)
+  const bool second = rowg >= pa.rows;
+  XkPart w;  // (field by field: scalar selects, no indexed copy of the arguments)
+  w.q = second ? pb.q : pa.q;
+  w.h = second ? pb.h : pa.h;
+  w.s = second ? pb.s : pa.s;
+  w.rows = second ? pb.rows : pa.rows;
+  w.q6 = second ? pb.q6 : pa.q6;
+  const int row0 = second ? rowg - pa.rows : rowg;
+  float r;
+  if constexpr (BODY == 3) {
+    if (w.q6) r = xk_rows<R, true>(w, row0, nsb, act, s_a);
+    else r = xk_rows<R, false>(w, row0, nsb, act, s_a);
+  } else {
+    r = xk_rows<R, false>(w, row0, nsb, act, s_a);
+  }
+  if constexpr (ROLE == XL_GELU) {
+    static_assert(ROLE != XL_GELU || R == 64, "GELU: 32 gate + 32 up rows per work-group");
+    if (t < 64) s_rows[t] = r;
+    __syncthreads();
+    if (t < 32) xl_gelu_store(s_rows, a, t);
+  } else {
+    if (t < R && row0 + t < w.rows) a.out[rowg + t] = r;
+  }
+}
+
+// repack: raw Q4_K (144 B) / Q6_K (210 B) blocks [rows][nsb] -> XL (exact.h); thread (sb, R, l8) moves one piece
+__global__ void xl_repack_kq_kernel(const uint8_t* __restrict__ q0, int r0, const uint8_t* __restrict__ q1, int r1,
+                                    const uint8_t* __restrict__ q2, bool gelu32, int rows, int nsb, int q6,
+                                    uint4* __restrict__ oq, uint2* __restrict__ oh, uint32_t* __restrict__ os) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)nsb * rows * 8) return;
+  const int l8 = (int)(i & 7);
+  const int R = (int)((i >> 3) % rows);
+  const int sb = (int)((i >> 3) / rows);
+  const uint8_t* q;
+  int sr;
+  if (gelu32) {  // gate 32 k.., up 32 k..
+    const int u = R / 64, k = R % 64;
+    q = k < 32 ? q0 : q1;
+    sr = 32 * u + (k & 31);
+  } else if (R < r0) {
+    q = q0; sr = R;
+  } else if (R < r0 + r1) {
+    q = q1; sr = R - r0;
+  } else {
+    q = q2; sr = R - r0 - r1;
+  }
+  uint32_t w[4] = {0, 0, 0, 0};
+  if (!q6) {
+    const uint8_t* blk = q + ((size_t)sr * nsb + sb) * 144;
+    const uint8_t* p = blk + 16 + 16 * l8;
+    for (int j = 0; j < 16; j++) w[j >> 2] |= (uint32_t)p[j] << (8 * (j & 3));
+    int sc, m;
+    // (ops.cpp:633-641, as scale_min_k4 of k_gemv.hip)
+    const uint8_t* s12 = blk + 4;
+    if (l8 < 4) { sc = s12[l8] & 63; m = s12[l8 + 4] & 63; }
+    else { sc = (s12[l8 + 4] & 0xF) | ((s12[l8 - 4] >> 6) << 4); m = (s12[l8 + 4] >> 4) | ((s12[l8] >> 6) << 4); }
+    const uint8_t* f = blk + ((l8 & 1) ? 2 : 0);  // even pieces: d, odd pieces: dmin
+    os[i] = (uint32_t)sc | ((uint32_t)m << 8) | ((uint32_t)f[0] << 16) | ((uint32_t)f[1] << 24);
+  } else {
+    const uint8_t* blk = q + ((size_t)sr * nsb + sb) * 210;
+    const int n = l8 >> 2, c = l8 & 3;
+    const uint8_t* ql = blk + 64 * n + 16 * c;
+    const uint8_t* qh = blk + 128 + 32 * n + 16 * (c & 1);
+    uint32_t hl = 0, hh = 0;  // quant j = 4 k + e: its two high bits at bit 8 e + 2 k
+    for (int j = 0; j < 16; j++) {
+      w[j >> 2] |= (uint32_t)ql[j] << (8 * (j & 3));
+      const int sh = 8 * (j & 3) + 2 * (j >> 2);
+      hl |= (uint32_t)((qh[j] >> (c < 2 ? 0 : 2)) & 3) << sh;
+      hh |= (uint32_t)((qh[j] >> (c < 2 ? 4 : 6)) & 3) << sh;
+    }
+    oh[i] = make_uint2(hl, hh);
+    os[i] = (uint32_t)blk[192 + 8 * n + c] | ((uint32_t)blk[192 + 8 * n + c + 4] << 8) | ((uint32_t)blk[208] << 16) |
+            ((uint32_t)blk[209] << 24);
+  }
+  oq[i] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // One work-group per token: the residual step + norm + quantize_row_q8_0 of the decode's XL_PRE prologue
 // (model.cpp:843-858 then 346-357, ops.cpp:116-139), or the embedding row * sqrt(n_embd) + attn_norm
 // (model.cpp:709-736), each serial chain by xl_sumsq; the Q8_0 blocks to global memory.
-template <int K4>
+// KQ: the K-convention XBlocks of q8k_block_quad instead (quantize_row_q8_k, ops.cpp:142-178: a wave's 64 float4 of a
+// k round are one super-block; q = the Q8_K quants, d = the super-block's d, nsum8 = the block's quant sum).
+template <int K4, bool KQ = false>
 __global__ __launch_bounds__(256) void xp_norm_kernel(XpNormArgs a) {
   constexpr int NW = 4, T = 256;
   extern __shared__ float4 s_n4[];
@@ -1733,6 +2133,21 @@ __global__ __launch_bounds__(256) void xp_norm_kernel(XpNormArgs a) {
     const bool ok = own(k);       // (whole octets: n4 and T are multiples of 8)
     const float4 x = make_float4((sc2 * hv[k].x) * nv[k].x, (sc2 * hv[k].y) * nv[k].y, (sc2 * hv[k].z) * nv[k].z,
                                  (sc2 * hv[k].w) * nv[k].w);
+    if constexpr (KQ) {
+      float d;
+      int bs16;
+      const uint32_t w = xk_q8k_wave(x, d, bs16);
+      const int bs32 = bs16 + __shfl_xor(bs16, 4);
+      const int i4 = k * T + t, b = i4 >> 3, sl = i4 & 7;
+      if (ok) {
+        reinterpret_cast<uint32_t*>(xq + b)[sl] = w;
+        if (sl == 0) {
+          xq[b].d = d;
+          xq[b].nsum8 = bs32;
+        }
+      }
+      continue;
+    }
     float amax = ok ? fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fmaxf(fabsf(x.z), fabsf(x.w))) : 0.0f;
     amax = fmaxf(amax, dpp_f<DPP_QUAD_1032>(amax));
     amax = fmaxf(amax, dpp_f<DPP_QUAD_2301>(amax));
@@ -1774,8 +2189,9 @@ typedef float xg_f2 __attribute__((ext_vector_type(2)));
 // type): out [T][ldo], or (hq) the GELU epilogue through s_r [64 rows][65] (LDS no longer read by the tile's loop)
 template <int RM, int RS>
 __device__ __forceinline__ void xg_finish(const float (&r)[4][4], float* s_r, int t, int rg, int tg, int row0, int tok0,
-                                          int rows, int T, float* __restrict__ out, int ldo, XBlock* __restrict__ hq) {
-  if (!hq) {
+                                          int rows, int T, float* __restrict__ out, int ldo, XBlock* __restrict__ hq,
+                                          float* __restrict__ hid = nullptr) {
+  if (!hq && !hid) {
 #pragma unroll
     for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -1796,12 +2212,14 @@ __device__ __forceinline__ void xg_finish(const float (&r)[4][4], float* s_r, in
   for (int tk = t >> 5; tk < XG_T; tk += 8) {
     const int tok = tok0 + tk;
     const float v = gelu_mul1<true>(s_r[u * 65 + tk], s_r[(32 + u) * 65 + tk]);
-    q8_block_store(v, tok < T, hq + (size_t)min(tok, T - 1) * nh + blockIdx.x, u);
+    if (hid && tok < T) hid[(size_t)tok * (nh * 32) + blockIdx.x * 32 + u] = v;  // (a K-quant down projection's input)
+    if (hq) q8_block_store(v, tok < T, hq + (size_t)min(tok, T - 1) * nh + blockIdx.x, u);
   }
 }
 __global__ __launch_bounds__(256, 2) void xp_gemm_kernel(const uint4* __restrict__ wq, const uint2* __restrict__ wd,
                                                          int rows, int nb, const XBlock* __restrict__ x, int T,
-                                                         float* __restrict__ out, int ldo, XBlock* __restrict__ hq) {
+                                                         float* __restrict__ out, int ldo, XBlock* __restrict__ hq,
+                                                         float* __restrict__ hid) {
   __shared__ __attribute__((aligned(16))) uint4 s_w[XG_CB][XG_R];      // the row's 16 nibble bytes of the block
   __shared__ float s_wd[XG_CB][XG_R];                                   // f16(w.d) / 16
   __shared__ __attribute__((aligned(16))) uint4 s_x[XG_CB][XG_T][2];   // the token's 32 quants
@@ -1904,7 +2322,7 @@ __global__ __launch_bounds__(256, 2) void xp_gemm_kernel(const uint4* __restrict
       const xg_f2* v = acc[i][j];  // v[s].x = a_s, v[s].y = a_(s + 4)
       r[i][j] = ((v[0].x + v[0].y) + (v[2].x + v[2].y)) + ((v[1].x + v[1].y) + (v[3].x + v[3].y));
     }
-  xg_finish<4, 1>(r, reinterpret_cast<float*>(&s_x[0][0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq);
+  xg_finish<4, 1>(r, reinterpret_cast<float*>(&s_x[0][0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq, hid);
 }
 
 // The same for a Q8_0 weight (exact.h): each (row, token) one chain over the blocks in order, sum = fmaf((float)dot *
@@ -1913,7 +2331,8 @@ __global__ __launch_bounds__(256, 2) void xp_gemm_kernel(const uint4* __restrict
 constexpr int XQ_CB = 8;
 __global__ __launch_bounds__(256, 2) void xp_gemm_q8_kernel(const uint4* __restrict__ wq, const uint2* __restrict__ wd,
                                                             int rows, int nb, const XBlock* __restrict__ x, int T,
-                                                            float* __restrict__ out, int ldo, XBlock* __restrict__ hq) {
+                                                            float* __restrict__ out, int ldo, XBlock* __restrict__ hq,
+                                                            float* __restrict__ hid) {
   __shared__ __attribute__((aligned(16))) uint4 s_q[2][XQ_CB][64][2];  // [0]: the rows' 32 quants, [1]: the tokens'
   __shared__ float s_wd[XQ_CB][XG_R];                                  // f16(w.d)
   __shared__ float s_xd[XQ_CB][XG_T];
@@ -1988,7 +2407,124 @@ __global__ __launch_bounds__(256, 2) void xp_gemm_q8_kernel(const uint4* __restr
     }
     __syncthreads();  // the chunk's LDS is refilled next
   }
-  xg_finish<1, 16>(acc, reinterpret_cast<float*>(&s_q[0][0][0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq);
+  xg_finish<1, 16>(acc, reinterpret_cast<float*>(&s_q[0][0][0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq, hid);
+}
+
+// The same for one part of a K-quant weight (exact.h) on the tokens' K-convention XBlocks: each (row, token) one
+// chain over the super-blocks in order -- Q4_K: sum = sum + t over the eight sub-blocks' t = fmaf((float)a, d sc,
+// -((dmin m) (float)bs)); Q6_K: sum = fmaf((float)part, d, sum) over the two halves -- with the same roundings as the
+// decode rows (xk_q4k_piece / xk_q6k_piece) and the per-op kernels.  One super-block of the rows' pieces and of the
+// tokens' quants is staged in LDS at a time; thread (rg, tg) owns rows rg + 16 i and tokens 4 tg + j.
+template <bool Q6>
+__global__ __launch_bounds__(256, 2) void xp_gemm_kq_kernel(XkPart w, int nsb, const XBlock* __restrict__ x, int T,
+                                                            float* __restrict__ out, int ldo, XBlock* __restrict__ hq,
+                                                            float* __restrict__ hid) {
+  __shared__ __attribute__((aligned(16))) uint4 s_wq[XG_R][9];   // (+1: a wave's 16 rows 36 banks apart)
+  __shared__ uint2 s_wh[Q6 ? XG_R : 1][9];
+  __shared__ uint32_t s_ws[XG_R][9];
+  __shared__ __attribute__((aligned(16))) int4 s_xq[XG_T][17];   // the token's 16 groups of 16 quants
+  __shared__ int s_xbs[XG_T][17];                                // their sums
+  __shared__ float s_xd[XG_T];
+  static_assert(sizeof(s_xq) >= 64 * 65 * 4, "the GELU epilogue's staging");
+  const int t = threadIdx.x, rg = t & 15, tg = t >> 4;
+  const int rows = w.rows, row0 = blockIdx.x * XG_R, tok0 = blockIdx.y * XG_T, nb = nsb * 8;
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[i][j] = 0.0f;
+  for (int sb = 0; sb < nsb; sb++) {
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+      const int i = t + 256 * m, l8 = i & 7, R = i >> 3;
+      const bool in = row0 + R < rows;
+      const size_t pc = ((size_t)sb * rows + row0 + (in ? R : 0)) * 8 + l8;
+      s_wq[R][l8] = in ? w.q[pc] : make_uint4(0, 0, 0, 0);
+      s_ws[R][l8] = in ? w.s[pc] : 0u;
+      if constexpr (Q6) s_wh[R][l8] = in ? w.h[pc] : make_uint2(0, 0);
+    }
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+      const int i = t + 256 * m, half = i & 1, b = (i >> 1) & 7, tk = i >> 4, tok = tok0 + tk;
+      const bool in = tok < T;
+      const XBlock* xb = x + (size_t)(in ? tok : 0) * nb + 8 * sb + b;
+      const int4 v = in ? (half ? xb->hi : xb->lo) : make_int4(0, 0, 0, 0);
+      s_xq[tk][2 * b + half] = v;
+      s_xbs[tk][2 * b + half] = sdot4(v.x, 0x01010101, sdot4(v.y, 0x01010101, sdot4(v.z, 0x01010101, sdot4(v.w, 0x01010101, 0))));
+    }
+    if (t < XG_T) s_xd[t] = tok0 + t < T ? x[(size_t)(tok0 + t) * nb + 8 * sb].d : 0.0f;
+    __syncthreads();
+    float xd[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) xd[j] = s_xd[4 * tg + j];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int row = rg + 16 * i;
+      if constexpr (Q6) {
+        const float wd = h2f((uint16_t)(s_ws[row][0] >> 16));
+#pragma unroll 1
+        for (int n = 0; n < 2; n++) {  // (rolled: the unrolled tile does not fit the registers of two work-groups per CU)
+          int part[4] = {0, 0, 0, 0};
+#pragma unroll 1
+          for (int c = 0; c < 4; c++) {
+            const uint4 q = s_wq[row][4 * n + c];
+            const uint2 hb = s_wh[row][4 * n + c];
+            const uint32_t sw = s_ws[row][4 * n + c];
+            const uint32_t w4[4] = {q.x, q.y, q.z, q.w};
+            int ql[4], qh[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              ql[k] = (int)((w4[k] & 0x0F0F0F0Fu) | (((hb.x >> (2 * k)) & 0x03030303u) << 4));
+              qh[k] = (int)(((w4[k] >> 4) & 0x0F0F0F0Fu) | (((hb.y >> (2 * k)) & 0x03030303u) << 4));
+            }
+            const int scl = (int)(int8_t)(sw & 0xFFu), sch = (int)(int8_t)((sw >> 8) & 0xFFu);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+              const int tk = 4 * tg + j, g = 8 * n + c;
+              const int4 xl = s_xq[tk][g], xh = s_xq[tk][g + 4];
+              const int dl = sdot4(ql[0], xl.x, sdot4(ql[1], xl.y, sdot4(ql[2], xl.z, sdot4(ql[3], xl.w, 0))));
+              const int dh = sdot4(qh[0], xh.x, sdot4(qh[1], xh.y, sdot4(qh[2], xh.z, sdot4(qh[3], xh.w, 0))));
+              part[j] += scl * (dl - 32 * s_xbs[tk][g]) + sch * (dh - 32 * s_xbs[tk][g + 4]);
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < 4; j++) acc[i][j] = fmaf((float)part[j], __fmul_rn(wd, xd[j]), acc[i][j]);
+        }
+      } else {
+#pragma unroll 1
+        for (int p = 0; p < 4; p++) {  // (rolled: as the Q6_K form)
+          const uint4 wa = s_wq[row][2 * p], wb = s_wq[row][2 * p + 1];  // q4 bytes 32 p .. 32 p + 31
+          const uint32_t sw0 = s_ws[row][2 * p], sw1 = s_ws[row][2 * p + 1];
+          const float wd = h2f((uint16_t)(sw0 >> 16)), wdmin = h2f((uint16_t)(sw1 >> 16));
+          const float sc0 = (float)(sw0 & 0xFFu), m0 = (float)((sw0 >> 8) & 0xFFu);
+          const float sc1 = (float)(sw1 & 0xFFu), m1 = (float)((sw1 >> 8) & 0xFFu);
+          const uint32_t w8[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+          int nl[8], nh[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++) {
+            nl[k] = (int)(w8[k] & 0x0F0F0F0Fu);
+            nh[k] = (int)((w8[k] >> 4) & 0x0F0F0F0Fu);
+          }
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            const int tk = 4 * tg + j;
+            const int4 x0 = s_xq[tk][4 * p], x1 = s_xq[tk][4 * p + 1], x2 = s_xq[tk][4 * p + 2], x3 = s_xq[tk][4 * p + 3];
+            int a0 = sdot4(nl[0], x0.x, sdot4(nl[1], x0.y, sdot4(nl[2], x0.z, sdot4(nl[3], x0.w, 0))));
+            a0 = sdot4(nl[4], x1.x, sdot4(nl[5], x1.y, sdot4(nl[6], x1.z, sdot4(nl[7], x1.w, a0))));
+            int a1 = sdot4(nh[0], x2.x, sdot4(nh[1], x2.y, sdot4(nh[2], x2.z, sdot4(nh[3], x2.w, 0))));
+            a1 = sdot4(nh[4], x3.x, sdot4(nh[5], x3.y, sdot4(nh[6], x3.z, sdot4(nh[7], x3.w, a1))));
+            const int bs0 = s_xbs[tk][4 * p] + s_xbs[tk][4 * p + 1], bs1 = s_xbs[tk][4 * p + 2] + s_xbs[tk][4 * p + 3];
+            const float d = __fmul_rn(wd, xd[j]), mn = __fmul_rn(wdmin, xd[j]);
+            const float t0 = fmaf((float)a0, __fmul_rn(d, sc0), -__fmul_rn(__fmul_rn(mn, m0), (float)bs0));
+            const float t1 = fmaf((float)a1, __fmul_rn(d, sc1), -__fmul_rn(__fmul_rn(mn, m1), (float)bs1));
+            acc[i][j] = __fadd_rn(__fadd_rn(acc[i][j], t0), t1);
+          }
+        }
+      }
+    }
+    __syncthreads();  // the super-block's LDS is refilled next
+  }
+  xg_finish<1, 16>(acc, reinterpret_cast<float*>(&s_xq[0][0]), t, rg, tg, row0, tok0, rows, T, out, ldo, hq, hid);
 }
 
 }  // namespace
@@ -2018,8 +2554,52 @@ bool xl_supported(const DevWeight& w) {
   return (w.type == T_Q4_0 || w.type == T_Q8_0) && !w.slab && w.cols % 128 == 0 && w.rows > 0;
 }
 
+bool xl_kq_supported(const DevWeight& w) {
+  return (w.type == T_Q4_K || w.type == T_Q6_K) && !w.kq && w.cols % 256 == 0 && w.rows > 0;
+}
+
+// a K-quant XL weight: the leading sources of one type, the rest (q|k Q4_K, v Q6_K) as its tail
+static XlWeight make_xl_kq_weight(const XlSrc& src, hipStream_t s) {
+  const int cols = src.w[0]->cols;
+  int n0 = 0;
+  while (n0 < src.n && src.w[n0]->type == src.w[0]->type) n0++;
+  if (src.gelu32 && n0 != src.n) throw std::runtime_error("xl: gate and up of different types");
+  XlWeight x;
+  x.nb = cols / 32;
+  x.type = src.w[0]->type;
+  for (int k = 0; k < n0; k++) {
+    if (!xl_kq_supported(*src.w[k]) || src.w[k]->cols != cols) throw std::runtime_error("xl: unsupported weight");
+    x.rows += src.w[k]->rows;
+    x.bytes += src.w[k]->bytes;
+  }
+  if (src.gelu32 && (src.w[0]->rows != src.w[1]->rows || src.w[0]->rows % 32)) throw std::runtime_error("xl: gelu32 rows");
+  if (x.rows % 64) throw std::runtime_error("xl: K-quant rows % 64 != 0");
+  const bool q6 = x.type == T_Q6_K;
+  const size_t nsb = (size_t)cols / 256, pieces = nsb * x.rows * 8;
+  if (pieces * 16 >= ((size_t)1 << 31)) throw std::runtime_error("xl: weight exceeds the 32-bit load offsets");
+  x.qs = static_cast<uint4*>(dev_alloc(pieces * 16 + 256));
+  x.sw = static_cast<uint32_t*>(dev_alloc(pieces * 4 + 256));
+  if (q6) x.qh = static_cast<uint2*>(dev_alloc(pieces * 8 + 256));
+  auto Q = [&](int k) { return k < n0 ? static_cast<const uint8_t*>(src.w[k]->qs) : nullptr; };
+  auto R = [&](int k) { return k < n0 ? src.w[k]->rows : 0; };
+  hipLaunchKernelGGL(xl_repack_kq_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, Q(0), R(0), Q(1), R(1),
+                     Q(2), src.gelu32, x.rows, (int)nsb, q6 ? 1 : 0, x.qs, x.qh, x.sw);
+  LLMI_HIP(hipGetLastError());
+  if (n0 < src.n) {
+    XlSrc rest;
+    for (int k = n0; k < src.n; k++) rest.w[rest.n++] = src.w[k];
+    x.tail = new XlWeight(make_xl_kq_weight(rest, s));
+    if (x.tail->tail) {  // (q, k, v of three alternating types: setup_xl does not ask for it)
+      free_xl_weight(x);
+      throw std::runtime_error("xl: more than two K-quant parts");
+    }
+  }
+  return x;
+}
+
 XlWeight make_xl_weight(const XlSrc& src, hipStream_t s) {
   if (src.n < 1 || src.n > 3 || (src.gelu32 && src.n != 2)) throw std::runtime_error("xl: bad sources");
+  if (src.w[0]->type == T_Q4_K || src.w[0]->type == T_Q6_K) return make_xl_kq_weight(src, s);
   const int cols = src.w[0]->cols;
   int rows = 0;
   size_t bytes = 0;
@@ -2058,6 +2638,12 @@ XlWeight make_xl_weight(const XlSrc& src, hipStream_t s) {
 void free_xl_weight(XlWeight& w) {
   dev_free(w.qs);
   dev_free(w.d);
+  dev_free(w.qh);
+  dev_free(w.sw);
+  if (w.tail) {
+    free_xl_weight(*w.tail);
+    delete w.tail;
+  }
   w = XlWeight{};
 }
 
@@ -2112,12 +2698,61 @@ static void launch_exact_gemv_q8(const XlWeight& w, const XlArgs& a, int role, h
   LLMI_HIP(hipGetLastError());
 }
 
+// K-quant weights: 256 lanes per work-group, 8 rows (PLAIN, QUANT, PRE; either row body) or the GELU role's 64 (Q4_K).
+// Dynamic LDS: the activation (n + n / 4 bytes, 4 B per super-block), then the larger of the prologue's operands (PRE /
+// GELU: 2 n floats) and the products' s_p (Q4_K 16896 B for 8 rows, 20480 B for 64; Q6_K 8704 B), which lies over them:
+//   n <= 1536 (XL_K4 2): 1952 + max(12288, 20480) = 22432 B
+//   n <= 3072 (XL_K4 3): 3888 + 24576            = 28464 B
+//   n <= 6144 (XL_K4 6): 7776 + 49152            = 56928 B
+// PLAIN / QUANT take any length the LDS holds (the 4B down rows: 10240 columns, 12960 + 16896 B).
+static void launch_exact_gemv_kq(const XlWeight& w, const XlArgs& a, int role, hipStream_t s) {
+  if (w.nb % 8 || w.rows % 64 || (w.tail && (w.tail->nb != w.nb || role == XL_GELU)))
+    throw std::runtime_error("exact gemv: bad K-quant weight");
+  const int nsb = w.nb / 8, n = nsb * 256;
+  auto part = [](const XlWeight* x) {
+    XkPart p;
+    p.q = x ? x->qs : nullptr;
+    p.h = x ? x->qh : nullptr;
+    p.s = x ? x->sw : nullptr;
+    p.rows = x ? x->rows : 0;
+    p.q6 = x && x->type == T_Q6_K ? 1 : 0;
+    return p;
+  };
+  if (role == XL_GELU && w.type != T_Q4_K) throw std::runtime_error("exact gemv: the GELU role takes Q4_K rows");
+  const bool pre = role == XL_PRE || role == XL_GELU;
+  const size_t sp = role == XL_GELU ? Xk<64, false>::SP_BYTES : std::max(Xk<8, false>::SP_BYTES, Xk<8, true>::SP_BYTES);
+  const size_t lds = (size_t)n + n / 4 + (size_t)((nsb + 3) & ~3) * 4 + std::max(pre ? (size_t)2 * n * 4 : 0, sp);
+  if (lds > 62 * 1024) throw std::runtime_error("exact gemv: activation exceeds LDS");
+  const int rows = w.rows + (w.tail ? w.tail->rows : 0);
+  auto go = [&](auto kern, int rpg) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)(rows / rpg)), dim3(256), lds, s, part(&w), part(w.tail), nsb, a);
+  };
+  const bool k2 = n <= 12 * 128, k3 = n <= 12 * 256;
+  switch (role) {
+    case XL_PLAIN: go(exact_gemv_kq_kernel<XL_PLAIN, 1, 8, 3>, 8); break;
+    case XL_QUANT: go(exact_gemv_kq_kernel<XL_QUANT, 1, 8, 3>, 8); break;
+    case XL_PRE:
+      if (k2) go(exact_gemv_kq_kernel<XL_PRE, 2, 8, 3>, 8);
+      else if (k3) go(exact_gemv_kq_kernel<XL_PRE, 3, 8, 3>, 8);
+      else go(exact_gemv_kq_kernel<XL_PRE, 6, 8, 3>, 8);
+      break;
+    case XL_GELU:
+      if (k2) go(exact_gemv_kq_kernel<XL_GELU, 2, 64, 1>, 64);
+      else if (k3) go(exact_gemv_kq_kernel<XL_GELU, 3, 64, 1>, 64);
+      else go(exact_gemv_kq_kernel<XL_GELU, 6, 64, 1>, 64);
+      break;
+    default: throw std::runtime_error("exact gemv: bad role");
+  }
+  LLMI_HIP(hipGetLastError());
+}
+
 void launch_exact_gemv(const XlWeight& w, const XlArgs& a_in, int role, hipStream_t s) {
   XlArgs a = a_in;
   if (!w.qs || w.nb % 4 || w.rows % 16) throw std::runtime_error("exact gemv: bad weight");
   if (role != XL_PLAIN && a.n != w.nb * 32) throw std::runtime_error("exact gemv: input length != cols");
   if (role == XL_GELU && w.rows % 64) throw std::runtime_error("exact gemv: GELU rows % 64 != 0");
   if ((role == XL_PRE || role == XL_GELU) && a.n > 24 * 256) throw std::runtime_error("exact gemv: n > 6144");
+  if (w.type == T_Q4_K || w.type == T_Q6_K) return launch_exact_gemv_kq(w, a, role, s);
   if (w.type == T_Q8_0) return launch_exact_gemv_q8(w, a, role, s);
   const size_t xe = (size_t)w.nb * 64 + (size_t)w.nb * 4;
   const size_t lds = xe + (role == XL_PLAIN ? 0 : (size_t)2 * a.n * 4);
@@ -2177,17 +2812,36 @@ void launch_exact_norm_batch(const XpNormArgs& a, int T, hipStream_t s) {
   if (a.table && a.type != T_F16 && a.type != T_F32 && a.type != T_Q8_0)
     throw std::runtime_error("exact norm batch: embedding table type");
   const size_t lds = (size_t)2 * a.n * 4;
-  if (a.n <= 3 * 4 * 256) hipLaunchKernelGGL(xp_norm_kernel<3>, dim3(T), dim3(256), lds, s, a);
+  if (a.q8k && a.n % 256) throw std::runtime_error("exact norm batch: Q8_K blocks need n % 256 == 0");
+  if (a.q8k) {
+    if (a.n <= 3 * 4 * 256) hipLaunchKernelGGL((xp_norm_kernel<3, true>), dim3(T), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((xp_norm_kernel<6, true>), dim3(T), dim3(256), lds, s, a);
+  } else if (a.n <= 3 * 4 * 256) hipLaunchKernelGGL(xp_norm_kernel<3>, dim3(T), dim3(256), lds, s, a);
   else hipLaunchKernelGGL(xp_norm_kernel<6>, dim3(T), dim3(256), lds, s, a);
   LLMI_HIP(hipGetLastError());
 }
 
-void launch_exact_gemm(const XlWeight& w, const XBlock* x, int T, float* out, int ldo, XBlock* hq, hipStream_t s) {
-  if (!w.qs || w.nb % 4 || w.rows % 16 || T <= 0 || !x || (!out && !hq)) throw std::runtime_error("exact gemm: bad arguments");
-  if (hq && w.rows % 64) throw std::runtime_error("exact gemm: GELU rows % 64 != 0");
+void launch_exact_gemm(const XlWeight& w, const XBlock* x, int T, float* out, int ldo, XBlock* hq, hipStream_t s,
+                       float* hid) {
+  if (!w.qs || w.nb % 4 || w.rows % 16 || T <= 0 || !x || (!out && !hq && !hid)) throw std::runtime_error("exact gemm: bad arguments");
+  if ((hq || hid) && w.rows % 64) throw std::runtime_error("exact gemm: GELU rows % 64 != 0");
   const dim3 grid((unsigned)((w.rows + XG_R - 1) / XG_R), (unsigned)((T + XG_T - 1) / XG_T));
-  if (w.type == T_Q8_0) hipLaunchKernelGGL(xp_gemm_q8_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq);
-  else hipLaunchKernelGGL(xp_gemm_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq);
+  if (w.type == T_Q4_K || w.type == T_Q6_K) {
+    if (w.nb % 8 || ((hq || hid) && (w.tail || w.type != T_Q4_K))) throw std::runtime_error("exact gemm: bad K-quant weight");
+    XkPart p;
+    p.q = w.qs;
+    p.h = w.qh;
+    p.s = w.sw;
+    p.rows = w.rows;
+    p.q6 = w.type == T_Q6_K ? 1 : 0;
+    if (p.q6) hipLaunchKernelGGL(xp_gemm_kq_kernel<true>, grid, dim3(256), 0, s, p, w.nb / 8, x, T, out, ldo, hq, hid);
+    else hipLaunchKernelGGL(xp_gemm_kq_kernel<false>, grid, dim3(256), 0, s, p, w.nb / 8, x, T, out, ldo, hq, hid);
+    LLMI_HIP(hipGetLastError());
+    if (w.tail) launch_exact_gemm(*w.tail, x, T, out + w.rows, ldo, nullptr, s, nullptr);  // (v's rows after q|k's)
+    return;
+  }
+  if (w.type == T_Q8_0) hipLaunchKernelGGL(xp_gemm_q8_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq, hid);
+  else hipLaunchKernelGGL(xp_gemm_kernel, grid, dim3(256), 0, s, w.qs, w.d, w.rows, w.nb, x, T, out, ldo, hq, hid);
   LLMI_HIP(hipGetLastError());
 }
 

@@ -513,6 +513,8 @@ void Session::build_rope_tables() {
 
 Session::Session(const uint8_t* gguf, size_t size, const llmi_session_opts& opts) : opts_(opts) {
   exact_ = (opts.flags & LLMI_EXACT) != 0;
+  exact_kq_ = exact_ && (opts.flags & LLMI_EXACT_KQ) != 0;
+  if (const char* e = getenv("LLMI_EXACT_KQ")) exact_kq_ = exact_kq_ || (exact_ && atoi(e) != 0);
   ex_gemv_ = ex_norm_ = ex_attn_ = ex_logits_ = exact_;
   if (const char* e = getenv("LLMI_EXACT_PARTS")) {  // diagnostics: mix exact/fast kernel families
     const std::string s(e);
@@ -828,8 +830,10 @@ void Session::record_step(hipStream_t s, bool gen, bool fold_embed, bool logits)
   bool fused = fuse_layers_;
   for (const auto& l : L_) fused &= l.fused;
   if (tp_ && !fused && !xl_) throw status_error(LLMI_E_ARG, "tensor parallel needs the fused layer path");
-  const bool xl_step =
-      xl_ && !dump_ && !(trace_fn_ && getenv("LLMI_TRACE_PER_OP")) && x_q8 && x_blocks == (const void*)act_.q8.xb;
+  // (a K-quant layer 0 takes xn_ itself: record_layers_xl quantizes it to Q8_K)
+  const bool xl_kq0 = xl_ && (L_[0].xqkv.type == T_Q4_K || L_[0].xqkv.type == T_Q6_K);
+  const bool xl_step = xl_ && !dump_ && !(trace_fn_ && getenv("LLMI_TRACE_PER_OP")) &&
+                       (xl_kq0 || (x_q8 && x_blocks == (const void*)act_.q8.xb));
   // an exact tensor-parallel rank has only the exact-order engine's shards (record_layers runs whole matrices
   // and has no exchanges): refuse rather than produce a wrong step
   if (tp_ && exact_ && !xl_step)
@@ -1393,8 +1397,13 @@ void Session::record_layers_fused(hipStream_t s, bool x_q8) {
 
 // Exact mode on the exact-order engine (exact.h): every Gemma-3 layer whose q, k, v, o, gate, up and down are each
 // Q4_0 or Q8_0 (the 4B / 1B / 27B Q4_0 files, the 1B Q8_0 file) gets XL copies of its weights -- q/k/v of one type,
-// gate/up of one type, since each pair is one XL weight; tensor-parallel sessions: Q4_0 only.  LLMI_EXACT_XL=0
-// keeps the per-op exact kernels.
+// gate/up of one type, since each pair is one XL weight; tensor-parallel sessions: Q4_0 only.  With LLMI_EXACT_KQ
+// (flag or environment; one device) each of q|k|v, o, gate|up and down may instead be of the K family (Q4_K / Q6_K,
+// columns % 256 == 0; the 4B Q4_K_M file): q, k, v each Q4_K or Q6_K with at most one change of type along q, k, v
+// (Q4_K_M: q|k Q4_K, v Q6_K -- one launch, the row body by a uniform branch); gate and up both Q4_K (both Q6_K is
+// turned away: the GELU role has the Q4_K body only); o and down either.  The families may differ from launch to
+// launch (each prologue produces the activation format its weight reads), not inside one.  LLMI_EXACT_XL=0 keeps the
+// per-op exact kernels.
 void Session::setup_xl() {
   if (!exact_ || hp_.gemma4 || ple_table_.qs || getenv("LLMI_EXACT_PARTS")) return;
   if (const char* e = getenv("LLMI_EXACT_XL"))
@@ -1406,13 +1415,28 @@ void Session::setup_xl() {
   for (const auto& l : L_) {
     bool ok = l.has_kv && !l.qkv.empty() && !l.gate_up.empty() && (hp_.n_head * l.hd) % 128 == 0 &&
               exact_attn_supported(l.hd, hp_.n_head, hp_.n_head_kv);
-    for (const auto& p : l.qkv) ok = ok && xl_supported(p.w) && p.w.type == l.qkv[0].w.type;
-    for (const auto& p : l.gate_up) ok = ok && xl_supported(p.w) && p.w.type == l.gate_up[0].w.type;
+    const bool kq = exact_kq_ && !tp_;
+    auto one = [&](const DevWeight& w) { return xl_supported(w) || (kq && xl_kq_supported(w) && w.rows % 64 == 0); };
+    if (ok && kq && xl_kq_supported(l.qkv[0].w)) {
+      int changes = 0;
+      for (size_t k = 0; k < l.qkv.size(); k++) {
+        ok = ok && xl_kq_supported(l.qkv[k].w) && l.qkv[k].w.rows % 64 == 0;
+        if (k > 0 && l.qkv[k].w.type != l.qkv[k - 1].w.type) changes++;
+      }
+      ok = ok && changes <= 1;
+    } else {
+      for (const auto& p : l.qkv) ok = ok && xl_supported(p.w) && p.w.type == l.qkv[0].w.type;
+    }
+    if (ok && kq && xl_kq_supported(l.gate_up[0].w)) {
+      for (const auto& p : l.gate_up) ok = ok && xl_kq_supported(p.w) && p.w.type == T_Q4_K;
+    } else {
+      for (const auto& p : l.gate_up) ok = ok && xl_supported(p.w) && p.w.type == l.gate_up[0].w.type;
+    }
     if (tp_ && ok)
       for (const DevWeight* w : {&l.qkv[0].w, &l.gate_up[0].w, &l.o.w, &l.down.w}) ok = ok && w->type == T_Q4_0;
     int gu_rows = 0;
     for (const auto& p : l.gate_up) gu_rows += p.w.rows;
-    ok = ok && xl_supported(l.o.w) && xl_supported(l.down.w) && gu_rows == 2 * F && !l.gu_interleaved &&
+    ok = ok && one(l.o.w) && one(l.down.w) && gu_rows == 2 * F && !l.gu_interleaved &&
          (l.gate_up.size() == 1 || l.gate_up[0].w.rows == F) && l.down.w.cols == hp_.n_ff;
     if (!ok) return;
   }
@@ -1423,8 +1447,12 @@ void Session::setup_xl() {
       const int nb = gate.cols / 32;
       gate.rows = F;
       up = gate;
-      up.qs = static_cast<uint8_t*>(gate.qs) + (size_t)F * nb * (gate.type == T_Q8_0 ? 32 : 16);
-      up.d = gate.d + (size_t)F * nb;
+      if (gate.type == T_Q4_K || gate.type == T_Q6_K) {  // (the file's blocks, row after row)
+        up.qs = static_cast<uint8_t*>(gate.qs) + gguf_bytes(gate.type, F, gate.cols);
+      } else {
+        up.qs = static_cast<uint8_t*>(gate.qs) + (size_t)F * nb * (gate.type == T_Q8_0 ? 32 : 16);
+        up.d = gate.d + (size_t)F * nb;
+      }
       gate.bytes = up.bytes = gguf_bytes(gate.type, F, gate.cols);
     } else {
       up = l.gate_up[1].w;
@@ -1462,12 +1490,15 @@ void Session::setup_xl() {
 // One decode step's layers on the exact-order engine: per layer q|k|v (the previous layer's post-FFN norm and
 // residual + this layer's attn_norm in its prologue), q/k norm + rope + KV append, attention, o (its input
 // quantized in the prologue), gate|up (post-attention norm + residual + ffn_norm in the prologue, GELU * up and
-// the hidden Q8_0 blocks in the epilogue), down.  The residual stream alternates between resid_ and resid2_ (a
+// the hidden Q8_0 blocks in the epilogue), down.  A K-quant launch takes Q8_K instead: its o and down quantize the
+// attention's f32 output / the GELU epilogue's f32 hid in their prologues (XL_QUANT), layer 0's q|k|v reads the Q8_K
+// blocks of the embedding launch's xn_.  The residual stream alternates between resid_ and resid2_ (a
 // prologue's work-group 0 writes the new residual while the others still read the old one).
 void Session::record_layers_xl(hipStream_t s) {
   const int E = hp_.n_embd;
   float* ra = resid_;
   float* rb = resid2_;
+  auto is_kq = [](const XlWeight& w) { return w.type == T_Q4_K || w.type == T_Q6_K; };
   for (int l = 0; l < hp_.n_layer; l++) {
     LayerDev& Ld = L_[l];
     const int hd = Ld.hd;
@@ -1476,6 +1507,10 @@ void Session::record_layers_xl(hipStream_t s) {
     q.eps = hp_.eps;
     q.out = qkv_;
     if (l == 0) {  // the embedding launch wrote attn_norm(x)'s Q8_0 blocks
+      if (is_kq(Ld.xqkv)) {  // (and xn_: its Q8_K quants take the blocks' place)
+        launch_quantize_q8k_xblocks(xn_, E, act_.q8.xb, s);
+        kernels_per_token_++;
+      }
       q.xb = act_.q8.xb;
       launch_exact_gemv(Ld.xqkv, q, XL_PLAIN, s);
     } else {
@@ -1516,7 +1551,13 @@ void Session::record_layers_xl(hipStream_t s) {
     XlArgs o;
     o.xb = xa_xq_;
     o.out = o_out_ + (size_t)tp_rank_ * e_sh_;
-    launch_exact_gemv(Ld.xo, o, XL_PLAIN, s);
+    if (is_kq(Ld.xo)) {
+      o.y = attn_;
+      o.n = hp_.n_head * hd;
+      launch_exact_gemv(Ld.xo, o, XL_QUANT, s);
+    } else {
+      launch_exact_gemv(Ld.xo, o, XL_PLAIN, s);
+    }
     if (tp_) coll_->all_gather(o_out_, (size_t)e_sh_ * sizeof(float), s, px_take());
     XlArgs gu;
     gu.y = o_out_;
@@ -1534,7 +1575,13 @@ void Session::record_layers_xl(hipStream_t s) {
     XlArgs dn;
     dn.xb = hq_;
     dn.out = d_out_ + (size_t)tp_rank_ * e_sh_;
-    launch_exact_gemv(Ld.xdn, dn, XL_PLAIN, s);
+    if (is_kq(Ld.xdn)) {
+      dn.y = hid_;
+      dn.n = hp_.n_ff;
+      launch_exact_gemv(Ld.xdn, dn, XL_QUANT, s);
+    } else {
+      launch_exact_gemv(Ld.xdn, dn, XL_PLAIN, s);
+    }
     if (tp_) coll_->all_gather(d_out_, (size_t)e_sh_ * sizeof(float), s, px_take());
     kernels_per_token_ += 6;
   }
@@ -1555,6 +1602,7 @@ bool Session::xp_ok() const {
 void Session::exact_prefill(const int32_t* tokens, int n, int pos) {
   hipStream_t s = stream_;
   const int E = hp_.n_embd, F = hp_.n_ff;
+  auto is_kq = [](const XlWeight& w) { return w.type == T_Q4_K || w.type == T_Q6_K; };
   int chunk = 256;
   if (const char* c = getenv("LLMI_XP_CHUNK")) chunk = std::max(1, atoi(c));
   const int cap = std::min(chunk, n);
@@ -1575,6 +1623,9 @@ void Session::exact_prefill(const int32_t* tokens, int n, int pos) {
     xp_axq_ = dalloc<XBlock>((size_t)cap * (maxq / 32));
     xp_qh_ = dalloc<uint16_t>((size_t)cap * maxq);
     xp_sc_ = dalloc<double>((size_t)cap * hp_.n_head * max_ctx_);
+    bool kq_down = false;  // a K-quant down projection reads the Q8_K quants of the f32 hid
+    for (const auto& l : L_) kq_down = kq_down || is_kq(l.xdn);
+    if (kq_down) xp_hid_ = dalloc<float>((size_t)cap * F);
     xp_cap_ = cap;
   }
   for (int c0 = 0; c0 < n; c0 += cap) {
@@ -1590,6 +1641,7 @@ void Session::exact_prefill(const int32_t* tokens, int n, int pos) {
       na.xq = xp_xq_;
       na.n = E;
       na.eps = hp_.eps;
+      na.q8k = is_kq(Ld.xqkv) ? 1 : 0;
       if (l == 0) {
         na.table = embd_raw_;
         na.row_bytes = embd_row_bytes_;
@@ -1629,6 +1681,9 @@ void Session::exact_prefill(const int32_t* tokens, int n, int pos) {
       xa.qh = xp_qh_;
       launch_exact_attn_batch(xa, T, s);
       if (l + 1 == hp_.n_layer) break;  // the last layer's K / V are in the cache: nothing after it is kept
+      // (a K-quant o projection: the Q8_K quants of the attention's f32 rows, [T][n_head * head_dim] contiguous --
+      // super-blocks never straddle a token)
+      if (is_kq(Ld.xo)) launch_quantize_q8k_xblocks(xp_att_, T * hp_.n_head * Ld.hd, xp_axq_, s);
       launch_exact_gemm(Ld.xo, xp_axq_, T, xp_o_, E, nullptr, s);
       XpNormArgs nf;  // post-attention norm + residual, ffn_norm (model.cpp:843-858, 872-881)
       nf.y = xp_o_;
@@ -1638,8 +1693,14 @@ void Session::exact_prefill(const int32_t* tokens, int n, int pos) {
       nf.xq = xp_xq_;
       nf.n = E;
       nf.eps = hp_.eps;
+      nf.q8k = is_kq(Ld.xgu) ? 1 : 0;
       launch_exact_norm_batch(nf, T, s);
-      launch_exact_gemm(Ld.xgu, xp_xq_, T, nullptr, 0, xp_hq_, s);
+      if (is_kq(Ld.xdn)) {  // hid as f32, then its Q8_K quants ([T][F] contiguous)
+        launch_exact_gemm(Ld.xgu, xp_xq_, T, nullptr, 0, nullptr, s, xp_hid_);
+        launch_quantize_q8k_xblocks(xp_hid_, T * F, xp_hq_, s);
+      } else {
+        launch_exact_gemm(Ld.xgu, xp_xq_, T, nullptr, 0, xp_hq_, s);
+      }
       launch_exact_gemm(Ld.xdn, xp_hq_, T, xp_d_, E, nullptr, s);
     }
   }

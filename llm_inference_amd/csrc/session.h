@@ -108,6 +108,7 @@ class Session {
   void record_layers_fused(hipStream_t s, bool x_q8);
   // exact mode on the exact-order engine (k_exact.hip): Q4_0 Gemma-3 layers, reference arithmetic, streamed
   bool xl_ = false;
+  bool exact_kq_ = false;  // LLMI_EXACT_KQ: the exact-order engine also takes K-quant layers (setup_xl)
   double* xa_scores_ = nullptr;  // exact attention scores [n_head][max_ctx]
   XBlock* xa_xq_ = nullptr;      // exact attention output's Q8_0 blocks (the o projection's x)
   void setup_xl();
@@ -121,6 +122,7 @@ class Session {
   int32_t* xp_tok_ = nullptr;
   float *xp_resid_ = nullptr, *xp_o_ = nullptr, *xp_d_ = nullptr, *xp_qkv_ = nullptr, *xp_att_ = nullptr;
   XBlock *xp_xq_ = nullptr, *xp_hq_ = nullptr, *xp_axq_ = nullptr;
+  float* xp_hid_ = nullptr;  // [cap][n_ff] f32 (K-quant down projections)
   uint16_t* xp_qh_ = nullptr;
   double* xp_sc_ = nullptr;
   void prepare_act(uint32_t wtype, const float* x, int n, ActBuf& act, hipStream_t s);

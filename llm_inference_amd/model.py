@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (LLMI_EXACT, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, TP_ID_BYTES, TRACE_FN, SessionInfo,
+from ._lib import (LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, TP_ID_BYTES, TRACE_FN, SessionInfo,
                    SessionOpts, check, lib, ptr)
 from .gguf import GGUFFile
 
@@ -48,19 +48,23 @@ class TPGroup:
 class Model:
     def __init__(self, gguf, device: int = 0, exact: bool = False, max_ctx: int = 4096,
                  use_graph: bool = True, attn_split: int = 0, tp_rank: int = 0, tp_size: int = 1,
-                 tp_id: Optional[bytes] = None, tp_group: Optional["TPGroup"] = None, tp_peer: bool = False):
+                 tp_id: Optional[bytes] = None, tp_group: Optional["TPGroup"] = None, tp_peer: bool = False,
+                 exact_kq: bool = False):
         """tp_id (RCCL, one process per GPU), tp_group (ranks on one device,
         one host thread each) or tp_peer (one process per GPU, the one-shot
         push exchange: peer_handle() / peer_connect() before the first
         forward) makes this session rank tp_rank of a row-sharded
-        tensor-parallel group of tp_size (include/llmi.h)."""
+        tensor-parallel group of tp_size (include/llmi.h).  exact_kq (with
+        exact): K-quant layers run on the exact-order engine too
+        (LLMI_EXACT_KQ; the environment's LLMI_EXACT_KQ=1 does the same)."""
         buf = gguf if isinstance(gguf, np.ndarray) else np.frombuffer(gguf, np.uint8)
         buf = np.ascontiguousarray(buf)
         self._tp_id = C.create_string_buffer(bytes(tp_id), TP_ID_BYTES) if tp_id is not None else None
         if tp_id is not None and len(tp_id) != TP_ID_BYTES:
             raise ValueError(f"tp_id must be {TP_ID_BYTES} bytes")
         self._tp_group = tp_group  # keep the group alive as long as the session
-        flags = (LLMI_EXACT if exact else 0) | (0 if use_graph else LLMI_NO_GRAPH) | (LLMI_TP_PEER if tp_peer else 0)
+        flags = (LLMI_EXACT if exact else 0) | (0 if use_graph else LLMI_NO_GRAPH) | (LLMI_TP_PEER if tp_peer else 0) | \
+            (LLMI_EXACT_KQ if exact_kq else 0)
         opts = SessionOpts(device, flags,
                            max_ctx, attn_split, tp_rank, tp_size,
                            C.cast(self._tp_id, C.c_void_p) if self._tp_id is not None else None,
