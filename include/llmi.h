@@ -188,8 +188,33 @@ int llmi_session_trace(llmi_session* s, const int32_t* tokens, int n_tokens, int
 
 /* Greedy decode loop of main.cpp:172-224 kept on the device: token `first`
  * at position `pos`, then n_steps forwards, each feeding its argmax to the
- * next without a host round trip.  out_tokens[i] = argmax after step i. */
+ * next without a host round trip.  out_tokens[i] = argmax after step i (the sampled token when a sampler is
+ * set, below). */
 int llmi_session_generate(llmi_session* s, int32_t first, int pos, int n_steps, int32_t* out_tokens);
+
+/* Seeded temperature / top-k / top-p sampling in the device decode loop.  With a sampler set,
+ * llmi_session_generate / llmi_session_enqueue draw each token from the step's full logits (forward's, after the
+ * final soft-cap) instead of taking the argmax: the top_k candidates by (logit descending, id ascending; NaN never),
+ * integer weights floor(expf((l_i - l_0) / temperature) 2^32) with glibc's expf, the smallest prefix whose weight
+ * reaches top_p of the total, and one 24-bit draw from splitmix64(seed, position).  The result is a pure function
+ * of the logits' bits, the parameters, the seed and the position -- the same ids however the steps are chunked.
+ * forward / dump / trace ignore the sampler.  One device only: a tensor-parallel session refuses one (LLMI_E_ARG). */
+#define LLMI_SAMPLE_MAX_K 256
+typedef struct {
+  float temperature;  /* > 0; 0: greedy */
+  int top_k;          /* 1..LLMI_SAMPLE_MAX_K; 0: LLMI_SAMPLE_MAX_K */
+  float top_p;        /* (0, 1]; 1: off */
+  uint64_t seed;
+} llmi_sampler;
+/* NULL or temperature == 0: greedy (the default).  Invalid fields (temperature < 0 or NaN, top_k outside
+ * 0..LLMI_SAMPLE_MAX_K, top_p outside (0, 1] or NaN): LLMI_E_ARG, the message names the field.  Takes effect for
+ * the steps enqueued after it; no graph is captured again. */
+int llmi_session_set_sampler(llmi_session* s, const llmi_sampler* sp);
+/* op level, host logits, synchronous: the same kernels (temperature must be > 0).  pos: the position of the token
+ * whose logits these are.  cand / cand_q (LLMI_SAMPLE_MAX_K entries, may be NULL) receive the ordered candidates
+ * (-1 past the last) and their integer weights, *n_cand = K', *n_nucleus = n (each may be NULL). */
+int llmi_sample_logits(const float* logits, size_t n, const llmi_sampler* sp, int pos, int32_t* token,
+                       int32_t* cand, uint64_t* cand_q, int* n_cand, int* n_nucleus);
 
 /* Enqueue n_steps decode steps without waiting (bench); llmi_session_sync
  * waits and copies the produced tokens (may be NULL). */
@@ -232,6 +257,7 @@ typedef struct {
                                  blocks (Q4_0 layers, one device: the default), 5 int8 MFMA on Q8_0 / Q8_K blocks
                                  (LLMI_PREFILL_F16=0, Q8_0 weights, tensor-parallel ranks), 6 f16 for K-quant layers
                                  (LLMI_PREFILL_F16=1); 0 no batched prefill */
+  int sampling;               /* 1 while a sampler is set (llmi_session_set_sampler) */
 } llmi_session_info;
 int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
 
@@ -243,7 +269,9 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *   1 = F16 logits GEMV, 2 = the decode loop's screened token selection,
  *   3 = gate_up (+ norm prologue + GELU), 4 = down (+ Q8_0 prologue),
  *   5 = qkv / o / gate_up / down as standalone layer GEMVs (round-1 family),
- *   6, 7 = the removed layer / FFN engines (always 0 / 0).
+ *   6, 7 = the removed layer / FFN engines (always 0 / 0),
+ *   8 = the sampler's two launches (candidate selection + finalize) on the session's current logits, with the
+ *       session's sampler (temperature 1, top_k 64, top_p 0.95 when none is set); bytes = the logits row.
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

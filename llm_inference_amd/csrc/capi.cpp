@@ -119,7 +119,7 @@ struct llmi_session {
 extern "C" {
 
 const char* llmi_last_error(void) { return g_err.c_str(); }
-int llmi_version(void) { return 1; }
+int llmi_version(void) { return 2; }
 
 int llmi_init_ops(int device) {
   return guard([&] {
@@ -450,6 +450,50 @@ int llmi_session_generate(llmi_session* s, int32_t first, int pos, int n_steps, 
 
 int llmi_session_enqueue(llmi_session* s, int32_t first, int pos, int n_steps) {
   return guard([&] { s->s->enqueue(first, pos, n_steps); });
+}
+
+int llmi_session_set_sampler(llmi_session* s, const llmi_sampler* sp) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "null pointer");
+    s->s->set_sampler(sp);
+  });
+}
+
+int llmi_sample_logits(const float* logits, size_t n, const llmi_sampler* sp, int pos, int32_t* token,
+                       int32_t* cand, uint64_t* cand_q, int* n_cand, int* n_nucleus) {
+  return guard([&] {
+    if (!logits || !sp) throw status_error(LLMI_E_ARG, "null pointer");
+    validate_sampler(*sp);
+    if (!(sp->temperature > 0.0f)) throw status_error(LLMI_E_ARG, "sample_logits: temperature must be > 0");
+    int ept = 0;
+    if (n == 0 || n > (size_t)INT32_MAX || sample_groups((int)n, &ept) == 0)
+      throw status_error(LLMI_E_SIZE, "sample_logits: between 1 and 1,048,576 logits");
+    if (pos < 0) throw status_error(LLMI_E_ARG, "sample_logits: pos < 0");
+    Ctx& c = ctx();
+    float* ld = (float*)c.get(0, n * 4);
+    auto* surv = (unsigned long long*)c.get(1, (size_t)SAMPLE_MAX_GROUPS * SAMPLE_MAX_K * 8);
+    // slot 2: the parameters, the position, the outputs
+    uint8_t* misc = (uint8_t*)c.get(2, 256 + sizeof(SampleDbg));
+    auto* spd = (SamplerDev*)misc;
+    int32_t* posd = (int32_t*)(misc + 64);
+    auto* dbg = (SampleDbg*)(misc + 256);
+    LLMI_HIP(hipMemcpyAsync(ld, logits, n * 4, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(posd, &pos, 4, hipMemcpyHostToDevice, c.stream));
+    launch_set_sampler(spd, sp->temperature, sp->top_k == 0 ? LLMI_SAMPLE_MAX_K : sp->top_k, sp->top_p, sp->seed,
+                       c.stream);
+    launch_sample_select(ld, (int)n, spd, surv, c.stream);
+    launch_sample_finalize(surv, (int)n, spd, posd, nullptr, nullptr, nullptr, 0, nullptr, 0, dbg, c.stream);
+    SampleDbg h;
+    LLMI_HIP(hipMemcpyAsync(&h, dbg, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipStreamSynchronize(c.stream));
+    if (token) *token = h.token;
+    if (n_cand) *n_cand = h.n_cand;
+    if (n_nucleus) *n_nucleus = h.n_nucleus;
+    for (int i = 0; i < SAMPLE_MAX_K; i++) {
+      if (cand) cand[i] = h.cand[i];
+      if (cand_q) cand_q[i] = h.q[i];
+    }
+  });
 }
 
 int llmi_session_sync(llmi_session* s, int32_t* out_tokens, int n) {

@@ -1,0 +1,94 @@
+// k_sample.hip -- the sampler's two launches (sample.h): the multi-work-group candidate
+// selection over a logits row and the one-work-group finalize with the token feedback.  The decode loop's folded
+// form of the finalize (with the next step's embed_norm) is in k_session.hip.
+#include "sample.h"
+
+namespace llmi {
+
+__global__ void set_sampler_kernel(SamplerDev* d, float temperature, int top_k, float top_p, unsigned long long seed) {
+  d->temperature = temperature;
+  d->top_k = top_k;
+  d->top_p = top_p;
+  d->pad = 0;
+  d->seed = seed;
+}
+
+void launch_set_sampler(SamplerDev* d, float temperature, int top_k, float top_p, unsigned long long seed,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(set_sampler_kernel, dim3(1), dim3(1), 0, s, d, temperature, top_k, top_p, seed);
+  LLMI_HIP(hipGetLastError());
+}
+
+// work-group b: logits [b EPT 1024, (b + 1) EPT 1024) -> its top K keys in surv[b 256 ..], the other slots 0
+template <int EPT>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_select_kernel(const float* __restrict__ logits, int V,
+                                                                       const SamplerDev* __restrict__ sp,
+                                                                       unsigned long long* __restrict__ surv) {
+  __shared__ SampleShared sh;
+  const int t = threadIdx.x;
+  int K = sp->top_k;
+  if (K <= 0 || K > SAMPLE_MAX_K) K = SAMPLE_MAX_K;
+  const long long base = (long long)blockIdx.x * (EPT * SAMPLE_THREADS);
+  unsigned long long key[EPT];
+#pragma unroll
+  for (int k = 0; k < EPT; k++) {
+    const long long i = base + (long long)k * SAMPLE_THREADS + t;
+    key[k] = i < (long long)V ? sample_key(logits[i], (uint32_t)i) : 0ull;
+  }
+  const unsigned long long thr = sample_block_threshold<EPT>(key, K, sh);
+  if (t < SAMPLE_MAX_K) sh.key[t] = 0ull;
+  if (t == 0) sh.slot = 0u;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < EPT; k++)
+    if (key[k] != 0ull && key[k] >= thr) {
+      const unsigned slot = atomicAdd(&sh.slot, 1u);
+      if (slot < (unsigned)SAMPLE_MAX_K) sh.key[slot] = key[k];
+    }
+  __syncthreads();
+  if (t < SAMPLE_MAX_K) surv[(size_t)blockIdx.x * SAMPLE_MAX_K + t] = sh.key[t];
+}
+
+void launch_sample_select(const float* logits, int V, const SamplerDev* sp, unsigned long long* surv, hipStream_t s) {
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  if (ept == 4)
+    hipLaunchKernelGGL(sample_select_kernel<4>, dim3(g), dim3(SAMPLE_THREADS), 0, s, logits, V, sp, surv);
+  else if (ept == 8)
+    hipLaunchKernelGGL(sample_select_kernel<8>, dim3(g), dim3(SAMPLE_THREADS), 0, s, logits, V, sp, surv);
+  else
+    hipLaunchKernelGGL(sample_select_kernel<16>, dim3(g), dim3(SAMPLE_THREADS), 0, s, logits, V, sp, surv);
+  LLMI_HIP(hipGetLastError());
+}
+
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_finalize_kernel(
+    const unsigned long long* __restrict__ surv, int n_surv, const SamplerDev* __restrict__ sp,
+    int32_t* __restrict__ d_pos, int32_t* __restrict__ d_token, int32_t* __restrict__ ring,
+    int32_t* __restrict__ ring_idx, int ring_cap, unsigned long long* __restrict__ keys, int n_keys,
+    SampleDbg* __restrict__ dbg) {
+  __shared__ SampleShared sh;
+  const int pos = *d_pos;
+  const int tok = sample_finalize_block(surv, n_surv, sp, pos, dbg, sh);
+  if (threadIdx.x == 0 && d_token) {
+    const int i = *ring_idx;
+    for (int q = 0; q < n_keys; q++) keys[q] = 0ull;
+    *d_token = tok;
+    *d_pos = pos + 1;
+    if (i < ring_cap) ring[i] = tok;
+    *ring_idx = i + 1;
+  }
+}
+
+void launch_sample_finalize(const unsigned long long* surv, int V, const SamplerDev* sp, int32_t* d_pos,
+                            int32_t* d_token, int32_t* ring, int32_t* ring_idx, int ring_cap,
+                            unsigned long long* keys, int n_keys, SampleDbg* dbg, hipStream_t s) {
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  hipLaunchKernelGGL(sample_finalize_kernel, dim3(1), dim3(SAMPLE_THREADS), 0, s, surv, g * SAMPLE_MAX_K, sp, d_pos,
+                     d_token, ring, ring_idx, ring_cap, keys, n_keys, dbg);
+  LLMI_HIP(hipGetLastError());
+}
+
+}  // namespace llmi

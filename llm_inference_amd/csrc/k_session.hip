@@ -1,6 +1,7 @@
 // k_session.hip -- weight upload/repack and the fused glue kernels of the
 // decode step (residual + norms, GELU + quantize, argmax, token feedback).
 #include "session_kernels.h"
+#include "sample.h"
 #include "spec_chain.h"
 
 #include <mutex>
@@ -874,6 +875,68 @@ void launch_finalize_embed_norm(unsigned long long* keys, int n_keys, int shard,
     hipLaunchKernelGGL(finalize_embed_norm_kernel<false>, dim3(1), dim3(1024), (size_t)n * 4, s, keys, n_keys, shard,
                        d_token, d_pos, ring, ring_idx, ring_cap, type, table, row_bytes, emb_scale, resid, w, out, n,
                        eps);
+  LLMI_HIP(hipGetLastError());
+}
+
+// The sampled decode loop's form of finalize_embed_norm_kernel: the sampler's finalize (sample.h) picks the token,
+// thread 0 does the bookkeeping, and the next step's embedding row + first attn_norm follow in the same launch.
+template <bool EXACT>
+__global__ __launch_bounds__(1024) void sample_finalize_embed_norm_kernel(
+    const unsigned long long* __restrict__ surv, int n_surv, const SamplerDev* __restrict__ sp,
+    unsigned long long* __restrict__ keys, int n_keys, int32_t* __restrict__ d_token, int32_t* __restrict__ d_pos,
+    int32_t* __restrict__ ring, int32_t* __restrict__ ring_idx, int ring_cap, uint32_t type,
+    const uint8_t* __restrict__ table, size_t row_bytes, float emb_scale, float* __restrict__ resid,
+    const float* __restrict__ w, NormOut out, int n, double eps) {
+  extern __shared__ float s_h[];
+  __shared__ float sh[16];
+  __shared__ SampleShared ssh;
+  const int t = threadIdx.x;
+  const int pos = *d_pos;
+  const int tok = sample_finalize_block(surv, n_surv, sp, pos, nullptr, ssh);
+  if (t == 0) {
+    const int i = *ring_idx;
+    for (int q = 0; q < n_keys; q++) keys[q] = 0ull;
+    *d_token = tok;
+    *d_pos = pos + 1;
+    if (i < ring_cap) ring[i] = tok;
+    *ring_idx = i + 1;
+  }
+  const uint8_t* row = table + (size_t)tok * row_bytes;
+  float ev[NORM_EPT], wv[NORM_EPT];
+#pragma unroll
+  for (int k = 0; k < NORM_EPT; k++) {
+    const int i = t + k * 1024;
+    const bool ok = i < n;
+    ev[k] = ok ? deq_embed(type, row, i) * emb_scale : 0.0f;
+    wv[k] = ok ? w[i] : 0.0f;
+    if (ok) resid[i] = ev[k];
+  }
+  const float sc = rms_scale(sumsq_regs<EXACT>(ev, n, s_h, sh), n, eps);
+  float xv[NORM_EPT];
+#pragma unroll
+  for (int k = 0; k < NORM_EPT; k++) xv[k] = (sc * ev[k]) * wv[k];
+  norm_outputs(xv, n, out, s_h);
+}
+
+void launch_sample_finalize_embed_norm(const unsigned long long* surv, int V, const SamplerDev* sp,
+                                       unsigned long long* keys, int n_keys, int32_t* d_token, int32_t* d_pos,
+                                       int32_t* ring, int32_t* ring_idx, int ring_cap, uint32_t type,
+                                       const uint8_t* table, size_t row_bytes, float emb_scale, float* resid,
+                                       const float* w, const NormOut& out, int n, double eps, bool exact,
+                                       hipStream_t s) {
+  if (n > 1024 * NORM_EPT) throw std::runtime_error("embed_norm: n_embd > 8192");
+  if (type != T_F16 && type != T_F32 && type != T_Q8_0) throw std::runtime_error("finalize_embed_norm: table type");
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  if (exact)
+    hipLaunchKernelGGL(sample_finalize_embed_norm_kernel<true>, dim3(1), dim3(1024), (size_t)n * 4, s, surv,
+                       g * SAMPLE_MAX_K, sp, keys, n_keys, d_token, d_pos, ring, ring_idx, ring_cap, type, table,
+                       row_bytes, emb_scale, resid, w, out, n, eps);
+  else
+    hipLaunchKernelGGL(sample_finalize_embed_norm_kernel<false>, dim3(1), dim3(1024), (size_t)n * 4, s, surv,
+                       g * SAMPLE_MAX_K, sp, keys, n_keys, d_token, d_pos, ring, ring_idx, ring_cap, type, table,
+                       row_bytes, emb_scale, resid, w, out, n, eps);
   LLMI_HIP(hipGetLastError());
 }
 

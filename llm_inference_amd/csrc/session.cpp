@@ -782,13 +782,17 @@ NormOut Session::embed_out() const { return norm_out_for(L_[0].qkv, xn_, act_, e
 bool Session::embed_fold_ok() const {
   return use_graph_ && screen_ && (embd_.type == T_F16 || embd_.type == T_Q8_0) && !ple_table_.qs;
 }
+bool Session::sample_fold_ok() const {
+  return use_graph_ && (embd_.type == T_F16 || embd_.type == T_Q8_0) && !ple_table_.qs;
+}
 
-void Session::record_step(hipStream_t s, bool gen, bool fold_embed, bool logits) {
+void Session::record_step(hipStream_t s, bool gen, bool fold_embed, bool logits, bool sample) {
   kernels_per_token_ = 0;
   px_k_ = 0;
   rec_gen_ = gen;
+  rec_sample_ = sample && logits && !gen;
   scr_prepped_ = false;
-  rec_fold_ = fold_embed && gen && embed_fold_ok() && !dump_ && !trace_fn_;
+  rec_fold_ = fold_embed && (rec_sample_ ? sample_fold_ok() : gen && embed_fold_ok()) && !dump_ && !trace_fn_;
   const int E = hp_.n_embd;
   const float emb_scale = std::sqrt(static_cast<float>(E));  // model.cpp:337-338
   auto nout = [&](const std::vector<GemvPart>& consumer) { return norm_out_for(consumer, xn_, act_, ex_norm_); };
@@ -847,7 +851,7 @@ void Session::record_step(hipStream_t s, bool gen, bool fold_embed, bool logits)
     record_layers(s, x_q8);
   }
   if (logits) record_logits(s, gen);
-  rec_gen_ = scr_prepped_ = rec_fold_ = false;
+  rec_gen_ = scr_prepped_ = rec_fold_ = rec_sample_ = false;
 }
 
 void Session::record_logits(hipStream_t s, bool gen) {
@@ -873,6 +877,20 @@ void Session::record_logits(hipStream_t s, bool gen) {
     }
     dump("result_output", lg, v_rows_, s);  // model.cpp:1046
     tap("logits", -1, lg, (size_t)v_rows_ * 4, s);
+  }
+  if (rec_sample_) {  // the sampler on the full logits (a key the GEMV folded is dropped: the finalize zeroes it)
+    const float emb_scale = std::sqrt(static_cast<float>(E));
+    launch_sample_select(lg, v_rows_, d_sampler_, samp_surv_, s);
+    if (rec_fold_)
+      launch_sample_finalize_embed_norm(samp_surv_, v_rows_, d_sampler_, amax_key_, tp_size_, d_token_, d_pos_, ring_,
+                                        ring_idx_, max_ctx_, embd_.type, embd_raw_, embd_row_bytes_, emb_scale, resid_,
+                                        L_[0].attn_norm, embed_out(), E, hp_.eps, ex_norm_, s);
+    else
+      launch_sample_finalize(samp_surv_, v_rows_, d_sampler_, d_pos_, d_token_, ring_, ring_idx_, max_ctx_, amax_key_,
+                             tp_size_, nullptr, s);
+    kernels_per_token_ += 2;
+    tap("token", -1, d_token_, 4, s);
+    return;
   }
   if (!fold && !(gen && screen_)) {  // (the screened selection folds its own key; logits_ is stale then)
     launch_argmax(lg, v_rows_, key, s);
@@ -1796,10 +1814,11 @@ void Session::ensure_graph(int kind) {
   hipGraph_t& g = graphs_[kind];
   hipGraphExec_t& ge = graph_execs_[kind];
   if (!use_graph_ || ge) return;
-  const bool gen = kind == STEP_GEN;
+  const bool gen = kind == STEP_GEN, sample = kind == STEP_SAMPLE;
   LLMI_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
   try {
-    record_step(stream_, gen, gen, kind != STEP_HIDDEN);
+    record_step(stream_, gen, gen || sample, kind != STEP_HIDDEN, sample);
+    step_kernels_[kind] = kernels_per_token_;
   } catch (...) {
     hipGraph_t gg;
     (void)hipStreamEndCapture(stream_, &gg);
@@ -1824,6 +1843,7 @@ void Session::px_prepare() {
 
 void Session::run_step(int kind) {
   px_prepare();
+  if (kind == STEP_GEN && sampling_) kind = STEP_SAMPLE;
   if (kind == STEP_GEN && !screen_) kind = STEP_LOGITS;
   // a tensor-parallel rank keeps the logits of every step: the standalone exchanges of the skipped launches are
   // counted by every rank alike, but the argmax keys' all-gather is part of the logits tail
@@ -1832,7 +1852,8 @@ void Session::run_step(int kind) {
     ensure_graph(kind);
     LLMI_HIP(hipGraphLaunch(graph_execs_[kind], stream_));
   } else {
-    record_step(stream_, kind == STEP_GEN, false, kind != STEP_HIDDEN);
+    record_step(stream_, kind == STEP_GEN, false, kind != STEP_HIDDEN, kind == STEP_SAMPLE);
+    step_kernels_[kind] = kernels_per_token_;
   }
 }
 
@@ -1990,13 +2011,50 @@ void Session::enqueue(int32_t first, int pos, int n_steps) {
   if (pos < 0 || pos + n_steps > max_ctx_) throw status_error(LLMI_E_RANGE, "generate: context overflow");
   tp_guarded([&] {
     set_token_pos(first, pos, true);
-    if (n_steps > 0 && screen_ && embed_fold_ok()) {  // the folded step graph starts at layer 0: the first embedding here
+    // the folded step graph starts at layer 0: the first embedding here
+    if (n_steps > 0 && (sampling_ ? sample_fold_ok() : screen_ && embed_fold_ok())) {
       const int E = hp_.n_embd;
       launch_embed_norm(embd_.type, embd_raw_, embd_row_bytes_, d_token_, std::sqrt(static_cast<float>(E)), resid_,
                         L_[0].attn_norm, embed_out(), E, hp_.eps, ex_norm_, stream_);
     }
     for (int i = 0; i < n_steps; i++) run_step(STEP_GEN);
   });
+}
+
+void validate_sampler(const llmi_sampler& sp) {
+  if (!(sp.temperature >= 0.0f)) throw status_error(LLMI_E_ARG, "sampler: temperature must be >= 0 (0: greedy)");
+  if (sp.top_k < 0 || sp.top_k > LLMI_SAMPLE_MAX_K)
+    throw status_error(LLMI_E_ARG, "sampler: top_k must be in 0.." + std::to_string(LLMI_SAMPLE_MAX_K));
+  if (!(sp.top_p > 0.0f && sp.top_p <= 1.0f)) throw status_error(LLMI_E_ARG, "sampler: top_p must be in (0, 1]");
+}
+
+void Session::ensure_sampler_buffers() {
+  if (d_sampler_) return;
+  int ept = 0;
+  if (sample_groups(v_rows_, &ept) == 0) throw status_error(LLMI_E_ARG, "sampler: vocabulary over 1,048,576 rows");
+  d_sampler_ = dalloc<SamplerDev>(2);  // [0] the session's sampler, [1] time_kernel(8)'s when none is set
+  samp_surv_ = dalloc<unsigned long long>((size_t)SAMPLE_MAX_GROUPS * SAMPLE_MAX_K);
+  samp_dbg_ = dalloc<SampleDbg>(1);
+}
+
+// The decode loop's token rule.  The parameters are written in stream order (as set_token_pos writes its words), so
+// steps already enqueued keep theirs and the step graph is not captured again.
+void Session::set_sampler(const llmi_sampler* sp) {
+  ensure_usable();
+  if (sp) validate_sampler(*sp);
+  const bool on = sp && sp->temperature != 0.0f;
+  if (on && tp_) throw status_error(LLMI_E_ARG, "sampler: tensor-parallel sessions decode greedily only");
+  if (on) {
+    ensure_sampler_buffers();
+    launch_set_sampler(d_sampler_, sp->temperature, sp->top_k == 0 ? LLMI_SAMPLE_MAX_K : sp->top_k, sp->top_p,
+                       sp->seed, stream_);
+  }
+  const bool changed = on != sampling_;
+  sampling_ = on;
+  // info().kernels_per_token: when the loop's token rule changes, the decode loop's step as it will run now, where
+  // that step has been recorded (a call that changes nothing leaves it alone)
+  const int kind = on ? STEP_SAMPLE : screen_ ? STEP_GEN : STEP_LOGITS;
+  if (changed && step_kernels_[kind] > 0) kernels_per_token_ = step_kernels_[kind];
 }
 
 void Session::sync(int32_t* out, int n) {
@@ -2091,6 +2149,7 @@ void Session::info(llmi_session_info* o) const {
   for (const auto& l : L_) kv += (size_t)2 * nkv_ * l.hd * 2;
   o->kv_bytes_per_pos = kv;
   o->kernels_per_token = kernels_per_token_;
+  o->sampling = sampling_ ? 1 : 0;
 }
 
 void Session::time_kernel(int which, int reps, double* us, double* bytes) {
@@ -2117,6 +2176,37 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
     *bytes = (double)logits_w_.bytes;
     LLMI_HIP(hipMemsetAsync(amax_key_, 0, 8 * (size_t)tp_size_, stream_));
     LLMI_HIP(hipStreamSynchronize(stream_));
+    return;
+  }
+  if (which == 8) {  // the sampler's two launches on the current logits (no token feedback)
+    *us = *bytes = 0.0;
+    if (tp_ || reps <= 0) return;
+    ensure_sampler_buffers();
+    SamplerDev* sp = d_sampler_;
+    if (!sampling_) {  // the model card's, in a struct of the hook's own: the session's stays as it was set
+      sp = d_sampler_ + 1;
+      launch_set_sampler(sp, 1.0f, 64, 0.95f, 0ull, stream_);
+    }
+    std::vector<hipEvent_t> ev(2 * (size_t)reps);
+    for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+    LLMI_HIP(hipStreamSynchronize(stream_));
+    for (int r = 0; r < reps; r++) {
+      LLMI_HIP(hipEventRecord(ev[2 * r], stream_));
+      launch_sample_select(logits_, v_rows_, sp, samp_surv_, stream_);
+      launch_sample_finalize(samp_surv_, v_rows_, sp, d_pos_, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                             samp_dbg_, stream_);
+      LLMI_HIP(hipEventRecord(ev[2 * r + 1], stream_));
+    }
+    LLMI_HIP(hipStreamSynchronize(stream_));
+    double tot = 0;
+    for (int r = 0; r < reps; r++) {
+      float ms = 0;
+      LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
+      tot += ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    *us = tot * 1000.0 / reps;
+    *bytes = (double)v_rows_ * 4.0;
     return;
   }
   if (which == 2) {  // the decode loop's token selection: prep + screening GEMV + rescoring

@@ -11,6 +11,7 @@
 #include "collective.h"
 #include "exact.h"
 #include "gguf_reader.h"
+#include "sample.h"
 #include "session_kernels.h"
 
 namespace llmi {
@@ -19,6 +20,9 @@ struct status_error : std::runtime_error {
   int code;
   status_error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
+
+// throws LLMI_E_ARG naming the field (temperature < 0 or NaN, top_k outside 0..256, top_p outside (0, 1] or NaN)
+void validate_sampler(const llmi_sampler& sp);
 
 struct HParams {  // model.h:22-43 (Gemma-3 subset)
   std::string arch;
@@ -77,6 +81,7 @@ class Session {
   void forward_trace(const int32_t* tokens, int n_tokens, int pos, bool gen, llmi_trace_fn fn, void* user);
   void enqueue(int32_t first, int pos, int n_steps);
   void sync(int32_t* out_tokens, int n);
+  void set_sampler(const llmi_sampler* sp);  // null or temperature 0: greedy
   void info(llmi_session_info* out) const;
   void time_kernel(int which, int reps, double* us, double* bytes);
   void peer_handle(void* out) const;
@@ -94,8 +99,11 @@ class Session {
   // layer 0 (the decode-loop graph; enqueue launches the first embed_norm itself)
   // logits false: the layers and the final norm only (a prompt token whose logits nobody reads: model.cpp:983-1001
   // computes the logits of the last prompt position only)
-  void record_step(hipStream_t s, bool gen = false, bool fold_embed = false, bool logits = true);
+  // sample: the sampled decode loop's step -- forward's full logits, then the sampler's two launches in place of the
+  // argmax and the token feedback (fold_embed: the second carries the next step's embed_norm)
+  void record_step(hipStream_t s, bool gen = false, bool fold_embed = false, bool logits = true, bool sample = false);
   bool embed_fold_ok() const;
+  bool sample_fold_ok() const;  // embed_fold_ok() but for the screening
   NormOut embed_out() const;
   bool down_plain(const LayerDev& Ld) const;
   void record_logits(hipStream_t s, bool gen = false);  // xn_ / act_.x16 -> logits, argmax key, token feedback
@@ -133,8 +141,9 @@ class Session {
   int dup(const char* k) const { return dup_.find(k) != std::string::npos ? 2 : 1; }
   void set_token_pos(int32_t token, int pos, bool reset_ring);
   // the step graphs: STEP_LOGITS (forward: full logits + argmax), STEP_GEN (the decode loop: token id only, the
-  // next embedding folded in), STEP_HIDDEN (a prompt token before the last: no logits)
-  enum { STEP_LOGITS = 0, STEP_GEN = 1, STEP_HIDDEN = 2, N_STEP_KINDS = 3 };
+  // next embedding folded in), STEP_HIDDEN (a prompt token before the last: no logits), STEP_SAMPLE (the decode loop
+  // with a sampler set: full logits, then the sampler)
+  enum { STEP_LOGITS = 0, STEP_GEN = 1, STEP_HIDDEN = 2, STEP_SAMPLE = 3, N_STEP_KINDS = 4 };
   void ensure_graph(int kind);
   // llmi_session_dump: eager steps with print_tensor-format dumps (dump_ set)
   std::FILE* dump_ = nullptr;
@@ -222,6 +231,14 @@ class Session {
   bool rec_fold_ = false;      // record_step(fold_embed): record_logits ends with finalize + embed_norm
   void screen_norm(NormOut& o);  // the final norm also writes the screening's x16 blocks where they will be used
   int kernels_per_token_ = 0;
+  int step_kernels_[N_STEP_KINDS] = {};  // kernels_per_token_ of each step kind as last recorded
+  // the sampler (sample.h): its parameters live on the device, so setting them re-captures nothing
+  bool sampling_ = false;
+  bool rec_sample_ = false;   // record_step(sample)
+  SamplerDev* d_sampler_ = nullptr;
+  unsigned long long* samp_surv_ = nullptr;  // the select launch's survivors
+  SampleDbg* samp_dbg_ = nullptr;            // time_kernel(8)'s outputs
+  void ensure_sampler_buffers();
   std::string dup_;
   size_t weight_bytes_ = 0;
   // row-sharded tensor parallelism; tp_ = false and G = 1

@@ -4,6 +4,7 @@ device session of include/llmi.h.
     m = Model(gguf_bytes)                 # Model(GGUFFile&)  model.cpp:13-56
     logits = m.forward([tok, ...], pos)   # Model::forward     model.cpp:706-1049
     ids = m.generate(first, pos, n)       # main.cpp:172-224 greedy loop, on device
+    m.set_sampler(temperature=1.0, top_k=64, top_p=0.95, seed=1)   # ... or seeded sampling in the same loop
 """
 from __future__ import annotations
 
@@ -12,8 +13,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from ._lib import (LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, TP_ID_BYTES, TRACE_FN, SessionInfo,
-                   SessionOpts, check, lib, ptr)
+from ._lib import (LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, TP_ID_BYTES, TRACE_FN, Sampler,
+                   SessionInfo, SessionOpts, check, lib, ptr)
 from .gguf import GGUFFile
 
 
@@ -75,6 +76,7 @@ class Model:
         self.gguf = GGUFFile(buf)  # host-side metadata view (tokenizer etc.)
         self.info = self.get_info()
         self.vocab = self.info.vocab
+        self._sampler = None
 
     def get_info(self) -> SessionInfo:
         info = SessionInfo()
@@ -110,9 +112,34 @@ class Model:
         check(lib().llmi_session_trace(self.h, ptr(t), t.size, pos, 1 if gen else 0, fn, None))
         return out
 
-    def generate(self, first: int, pos: int, n_steps: int) -> np.ndarray:
+    def set_sampler(self, sampler: Optional[dict] = None, *, temperature: Optional[float] = None, top_k: int = 0,
+                    top_p: float = 1.0, seed: int = 0) -> None:
+        """llmi_session_set_sampler: generate / enqueue draw each token by seeded temperature / top-k / top-p
+        sampling instead of taking the argmax.  set_sampler(None) (or temperature 0)
+        restores greedy decoding.  A dict of the same keywords is accepted as the positional argument."""
+        if sampler is not None:
+            return self.set_sampler(**sampler)
+        if temperature is None:
+            check(lib().llmi_session_set_sampler(self.h, None))
+            self._sampler = None
+        else:
+            sp = Sampler(temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF)
+            check(lib().llmi_session_set_sampler(self.h, C.byref(sp)))
+            self._sampler = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed) if temperature else None
+        self.info = self.get_info()
+
+    def generate(self, first: int, pos: int, n_steps: int, sampler: Optional[dict] = None) -> np.ndarray:
+        """sampler (a dict of set_sampler's keywords): set for this call only, the session's own restored after."""
         out = np.zeros(max(n_steps, 1), np.int32)
-        check(lib().llmi_session_generate(self.h, first, pos, n_steps, ptr(out)))
+        if sampler is None:
+            check(lib().llmi_session_generate(self.h, first, pos, n_steps, ptr(out)))
+            return out[:n_steps]
+        before = self._sampler
+        self.set_sampler(**sampler)
+        try:
+            check(lib().llmi_session_generate(self.h, first, pos, n_steps, ptr(out)))
+        finally:
+            self.set_sampler(before)
         return out[:n_steps]
 
     def enqueue(self, first: int, pos: int, n_steps: int) -> None:

@@ -172,6 +172,26 @@ def gelu_mul(gate, up) -> np.ndarray:
     return out
 
 
+def sample_logits(logits, pos: int, temperature: float, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                  details: bool = False):
+    """llmi_sample_logits: one seeded temperature / top-k / top-p draw from a logits row with the decode loop's
+    kernels.  Returns the token; details=True: (token, cand, cand_q, n_nucleus) -- the K'
+    ordered candidate ids (int32), their integer weights (uint64) and the nucleus size."""
+    import ctypes as C
+    from ._lib import SAMPLE_MAX_K, Sampler
+    lg = _f32(logits).reshape(-1)
+    sp = Sampler(temperature, top_k, top_p, seed & 0xFFFFFFFFFFFFFFFF)
+    tok = np.zeros(1, np.int32)
+    cand = np.zeros(SAMPLE_MAX_K, np.int32)
+    cq = np.zeros(SAMPLE_MAX_K, np.uint64)
+    nc, nn = C.c_int(), C.c_int()
+    check(lib().llmi_sample_logits(ptr(lg), lg.size, C.byref(sp), pos, ptr(tok), ptr(cand), ptr(cq), C.byref(nc),
+                                   C.byref(nn)))
+    if not details:
+        return int(tok[0])
+    return int(tok[0]), cand[:nc.value].copy(), cq[:nc.value].copy(), nn.value
+
+
 class DeviceWeight:
     """A GGUF weight uploaded once (llmi_weight_create); multiply many times."""
 
