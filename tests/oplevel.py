@@ -20,6 +20,42 @@ Tolerances (per tensor, why):
                      vs the reference's f16-accumulator algorithm: that algorithm's
                      own drift from exact math (measured on the same inputs) + 4e-5.
   Q8_0 blocks        bit-identical (same floats in, ops.cpp:116-139 exactly).
+
+The batched prefill's non-GEMM kernels (OpChecker.prefill_ops; k_prefill.hip).  Kinds marked [b] hold EVERY
+element to a bound and report the worst |dev - ref| / bound (<= 1 passes); the others report a relative error
+of max as above; [=] is bit-identity (reported as 0).
+  quantised rows [b] a device block (d16, q) of a reference row x_ref known to tol (absolute), d_ref = max|x_ref
+                     block| / 127:  |d16 q - x_ref| <= (0.5 + 2^-10) d_ref + |q| (ulp_f16(d16)/2 + tol/127) + tol
+                     -- 0.5 d_ref the rounding of x/d to an integer, 2^-10 d_ref the f32 rounding of x (1/d),
+                     |q| ulp/2 the f16 rounding of the stored scale, |q| tol/127 the scale's share of the
+                     producer's error (tol of the block's largest element).  Q8_K: d = max/127 per 256 elements, an
+                     f32 (no f16 term).  f16 rows (x16 2^s = f16(d16 q 2^-s) 2^s): + 2^-11 |x| for the rounding of
+                     the 18-bit product d16 q to f16, + 2^-25 2^s where that f16 is subnormal; q and d recovered
+                     from the row (the block's largest element is d16 127).  And |q_dev - q_ref| <= 1 wherever
+                     tol / d_ref < 0.25 (q_ref: the oracle's quantize_row_q8_0 / _q8_k of x_ref).
+  token scales       2^s a power of two; the row's largest |x16| in [2^14, 2^15) widened by 2^-10 (d16 = f16(max/127)
+                     and f16(d16 127 2^-s): two f16 roundings); 1 for an all-zero row; no inf / NaN (token_xs).
+  pf_norm_in,        the quantised-row bound with tol = NORM_RTOL max|x_ref| (the norm's squared-sum tree); layer
+  pf_norm_ffn [b]    0's input is the oracle's embedding row * f32(sqrt(E)), bit-exact arithmetic.
+  pf_qk_q, pf_qk_k   |f16 - ref| <= 2^-10 |ref| + NORM_RTOL max|ref| per element (one f16 rounding + the squared-sum
+  [b]                tree; the rope tables are the reference's own floats); pf_qk_v [=] f16(v); cache rows past
+                     pos0 + T all zero (a fresh session's cache is zero-filled and nothing else writes there).
+  pf_attn [b]        the quantised-row bound around the float64 causal attention of the device's f16 q / K / V with
+                     tol_i = 2^-11 sum_t p_t |v_ti|                     (P rounded to f16 for the PV MFMA while
+                                                                          l_run sums the unrounded p)
+                           + 2^-25 sum_t |v_ti| / sum_t e^(s_t - max)   (f16 underflow of tiny p)
+                           + max_i sum_t p_t e_t |v_ti - o_i|           (fp32 scores: score_sensitivity's e_t =
+                                                                          2 sqrt(hd) 2^-24 sum_i |q_i k_ti|; with
+                                                                          a soft-cap + 4 2^-24 |s_t| for tanhf, the
+                                                                          division and the product)
+                           + ATTN_F64_RTOL sqrt(max(1, keys/256)) max|o| (fp32 split sums, as the decode check)
+  pf_resid_attn,     rtol NORM_RTOL of max (norm + one f32 add).
+  pf_resid_ffn
+  pf_gelu [b]        the quantised-row bound around the oracle's gelu_mul of the de-interleaved gate / up floats
+                     with tol = 2^-22 max|hid|: not bit-identical, because the prefill's GELU kernels use the device
+                     libm's tanhf (gelu_mul1<EXACT = false>), not glibc's -- Q8_K's f32 d shows the last-place
+                     differences that Q8_0's f16 d and the integer quants absorb (OpChecker._gelu_rows).
+  pf_tail            logits vs the oracle's output_norm + F16 GEMV of the final residual: GEMV_RTOL + 2 NORM_RTOL.
 """
 from __future__ import annotations
 
@@ -103,6 +139,92 @@ def rel_err(got, ref):
     return float(np.abs(np.asarray(got, np.float64) - ref).max() / max(float(np.abs(ref).max()), 1e-30))
 
 
+def f16_ulp(d):
+    """Spacing of the f16 grid at |d| (2^-24 in the subnormal range)."""
+    return np.spacing(np.abs(np.asarray(d, np.float64)).astype(np.float16)).astype(np.float64)
+
+
+def attn_key_splits(hd, G):
+    """Key tiles per round of prefill_attn_mfma_kernel (the launcher's S: attn_g in k_prefill.hip)."""
+    return 2 if hd >= 256 or (G == 4 and hd == 128) else 4
+
+
+def attn_check_tokens(T, pos0, S, t0=0):
+    """The query tokens prefill_ops checks: every token of the first and the last 32-query block and of each
+    block whose number of key rounds (ceil(key tiles / S)) differs from the block's before it; every eighth
+    token elsewhere; nothing before t0 (the last layer's trim)."""
+    nqb = (T + 31) // 32
+    rounds = [((pos0 + min(32 * b + 32, T) - 1) // 32 + 1 + S - 1) // S for b in range(nqb)]
+    full = {0, nqb - 1} | {b for b in range(1, nqb) if rounds[b] != rounds[b - 1]}
+    return [t for t in range(t0, T) if t // 32 in full or t % 8 == 0]
+
+
+def act_rows(D, l, proj, n_t, xs, ncols, kq):
+    """One pf_x_<proj> tap of n_t token rows (xs activation blocks each), its format from its size: XBlocks (48
+    B: Q8_K quants on K-quant layers, else Q8_0; the blocks' invariants asserted) or f16 rows with the token
+    scales 2^s of the pf_xs_<proj> tap (the attention's rows have none: 1)."""
+    b = D[(f"pf_x_{proj}", l)][-1]
+    rb = len(b) // n_t
+    assert rb * n_t == len(b) and rb in (48 * xs, 64 * xs), f"activation rows of {len(b)} B for {n_t} tokens"
+    if rb == 64 * xs:
+        x16 = np.frombuffer(b, np.float16).reshape(n_t, xs * 32)[:, :ncols].astype(np.float64)
+        assert np.isfinite(x16).all(), "token scales: an inf or NaN in an f16 row"
+        ts = np.ones(n_t)
+        if (f"pf_xs_{proj}", l) in D:
+            ts = f32(D[(f"pf_xs_{proj}", l)][-1]).astype(np.float64)
+            assert ts.size == n_t and np.all(ts > 0) and np.all(np.frexp(ts)[0] == 0.5), "token scales: powers of two"
+            mx = np.abs(x16).max(1)
+            ok = np.where(mx == 0, ts == 1.0, (mx >= 2.0 ** 14 * (1 - 2.0 ** -10)) & (mx < 2.0 ** 15 * (1 + 2.0 ** -10)))
+            bad = np.nonzero(~ok)[0]
+            assert bad.size == 0, (f"token scales: rows {bad[:8].tolist()} with max |x16| {mx[bad[:8]].tolist()} "
+                                   f"outside [2^14, 2^15) (2^s {ts[bad[:8]].tolist()})")
+        return {"kind": "f16", "x16": x16, "ts": ts, "bits": np.frombuffer(b, np.uint16).reshape(n_t, xs * 32)[:, :ncols]}
+    w = np.ascontiguousarray(np.frombuffer(b, np.uint32).reshape(n_t, xs, 12)[:, : ncols // 32])
+    (xblocks_q8k_to_f32 if kq else xblocks_to_q8_0)(w)  # the blocks' invariants
+    return {"kind": "q8_k" if kq else "q8_0", "words": w,
+            "q": w[:, :, :8].copy().view(np.int8).reshape(n_t, -1, 32).astype(np.float64),
+            "d": w[:, :, 8].copy().view(np.float32).astype(np.float64)}
+
+
+def quant_errors(R, x_ref, tol):
+    """The quantisation-aware bound (module docstring): rows R (act_rows) against the reference rows x_ref
+    [n_t][n] known to tol (absolute; a scalar, per row or per element).  Returns |dev - ref|, the bound, the
+    device's quants times the sign of d, and the per-block mask tol / d_ref < 0.25."""
+    n_t, n = x_ref.shape
+    B = 256 if R["kind"] == "q8_k" else 32
+    xr = np.asarray(x_ref, np.float64).reshape(n_t, n // B, B)
+    tl = np.broadcast_to(np.asarray(tol, np.float64), (n_t, n)).reshape(xr.shape)
+    d_ref = np.abs(xr).max(-1) / 127.0
+    tol_b = tl.max(-1)
+    extra = 0.0
+    if R["kind"] == "f16":  # recover (d, q) of every block: its largest element is f16(d16 127 2^-s)
+        x16 = R["x16"].reshape(xr.shape)
+        ts = R["ts"][:, None]
+        m = np.abs(x16).max(-1)
+        ms = np.where(m > 0, m, 1.0)[..., None]
+        qf = 127.0 * x16 / ms
+        q = np.rint(qf)
+        # x16 / m = (q / 127) (1 + e1) / (1 + e2), |e| <= 2^-11 (+ 2^-25 absolute where x16 is subnormal)
+        assert np.all(np.abs(qf - q) <= np.abs(q) * 2.0 ** -10 * 1.001 + 127.0 * 2.0 ** -25 * 1.001 / ms), \
+            "an f16 row is not f16(d q) of Q8_0 blocks"
+        d = m * ts / 127.0
+        xd = x16 * ts[..., None]
+        extra = 2.0 ** -11 * np.abs(xd) + 2.0 ** -25 * ts[..., None]
+        ulp = f16_ulp(d * (1 + 2.0 ** -10)) / 2  # d16 = f16(max / 127) is m 2^s / 127 to 2^-11: never the finer binade
+    elif R["kind"] == "q8_0":
+        q, d = R["q"], R["d"]
+        xd = d[..., None] * q
+        ulp = f16_ulp(d) / 2
+    else:
+        q = R["q"].reshape(xr.shape)
+        d = R["d"][:, ::8]
+        xd = d[..., None] * q
+        ulp = np.zeros_like(d)
+    bound = (0.5 + 2.0 ** -10) * d_ref[..., None] + np.abs(q) * (ulp + tol_b / 127.0)[..., None] + tl + extra
+    near = (d_ref > 0) & (tol_b < 0.25 * d_ref)
+    return np.abs(xd - xr), bound, q * np.where(d < 0, -1.0, 1.0)[..., None], near
+
+
 class Weights:
     """Raw GGUF weights of a synthetic Gemma-3 file, by reference tensor name."""
 
@@ -127,10 +249,13 @@ class OpChecker:
     """Checks one traced decode step (or prefill) op by op; records the
     worst relative error per tensor kind in self.report."""
 
-    def __init__(self, oracle, buf, cfg, max_ctx, threads=16, swa_pattern=None):
+    def __init__(self, oracle, buf, cfg, max_ctx, threads=16, swa_pattern=None, softcap=0.0, gelu_h=None):
+        """buf: the GGUF file's bytes, or an object with Weights' raw() / f32() (a test's stand-in); softcap: the
+        file's attention.logit_softcapping; gelu_h: the gate/up interleave group where n_embd is not in GELU_H."""
         self.orc, self.cfg, self.max_ctx, self.th = oracle, cfg, max_ctx, threads
         self.swa_pattern = swa_pattern
-        self.w = Weights(buf)
+        self.softcap, self.gelu_h = float(softcap), gelu_h
+        self.w = buf if hasattr(buf, "raw") else Weights(buf)
         self.eps = float(np.float32(cfg.eps))
         self.report = defaultdict(float)
 
@@ -310,6 +435,220 @@ class OpChecker:
                     self._prefill_f16_one(D, l, proj, names, ncols, nbytes // (64 * xs), H)
                 else:
                     self._prefill_q8_one(D, l, proj, names, ncols, nbytes // (48 * xs), H)
+
+    def bound(self, kind, err, bnd, what=""):
+        """Every element's |dev - ref| within its bound; reports the worst err / bound."""
+        err, bnd = np.asarray(err, np.float64), np.broadcast_to(np.asarray(bnd, np.float64), np.shape(err))
+        assert np.isfinite(err).all(), f"{kind}: {what}: a non-finite value"
+        ratio = np.where(err > 0, err / np.maximum(bnd, 1e-300), 0.0)
+        worst = float(ratio.max()) if ratio.size else 0.0
+        self.report[kind] = max(self.report[kind], worst)
+        if worst > 1.0:
+            i = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+            raise AssertionError(f"{kind}: {what} element {tuple(int(j) for j in i)}: |dev - ref| {err[i]:.6g} > bound "
+                                 f"{bnd[i]:.6g} ({int((ratio > 1).sum())} of {ratio.size} elements out)")
+
+    def quant_rows(self, kind, D, l, proj, n_t, ncols, x_ref, tol):
+        """pf_x_<proj> of layer l is an acceptable quantisation of the rows x_ref (the quantisation-aware bound of
+        the module docstring, every element; the quants within 1 of the oracle's where tol / d_ref < 0.25)."""
+        what = f"layer {l} pf_x_{proj}"
+        c = self.cfg
+        xs = max(c.n_embd, c.n_ff, c.n_head * c.head_dim) // 32  # activation blocks per token (session pf_xs_)
+        try:
+            R = act_rows(D, l, proj, n_t, xs, ncols, self.kq)
+            err, bnd, qs, near = quant_errors(R, x_ref, tol)
+        except AssertionError as e:
+            raise AssertionError(f"{kind}: {what}: {e}") from None
+        self.bound(kind, err, bnd, what)
+        x32 = np.ascontiguousarray(x_ref, np.float32)
+        if R["kind"] == "q8_k":
+            ref = np.stack([np.frombuffer(self.orc.quantize_q8_k(r), np.uint8).reshape(-1, 292) for r in x32])
+            q_ref = ref[:, :, 4:260].copy().view(np.int8).astype(np.float64)
+            q_ref = q_ref * np.where(ref[:, :, :4].copy().view(np.float32) < 0, -1.0, 1.0)
+        else:
+            ref = np.stack([np.frombuffer(self.orc.quantize_q8_0(r), np.uint8).reshape(-1, 34) for r in x32])
+            q_ref = ref[:, :, 2:].copy().view(np.int8).astype(np.float64)
+        dq = np.abs(qs - q_ref) * near[..., None]
+        assert dq.max() <= 1, f"{kind}: {what}: a quant {int(dq.max())} from the oracle's where tol < d_ref / 4"
+        self.report[kind + "_rows_" + R["kind"]] = max(self.report[kind + "_rows_" + R["kind"]], float(dq.max()))
+        return R
+
+    def norm_rows(self, x, wname):
+        return np.stack([self.norm(r, wname) for r in np.ascontiguousarray(x, np.float32)])
+
+    def prefill_ops(self, taps, tokens, pos0):
+        """One traced batched prefill of a single chunk (tokens at positions pos0.., T <= 512: one tap per name
+        and layer): every non-GEMM launch of k_prefill.hip from the device's own tapped input to it, against
+        float64 / the oracle -- the kinds, bounds and their derivations in the module docstring.  Per layer:
+        pf_norm_in (embedding or residual -> attn_norm rows), pf_qk_q / _k / _v (q/k norm, rope with the layer's
+        base, q scale, K/V append; cache rows past pos0 + T untouched: zero, a fresh session's cache being
+        zero-filled), pf_attn, pf_resid_attn, pf_norm_ffn, pf_gelu, pf_resid_ffn; then pf_tail (final residual,
+        output_norm, logits, token).  The last layer past its K/V append runs on the final token only (t0 = T - 1,
+        and on the int8 path for Q4_0 / Q8_0 layers): the row counts and formats follow from the tap sizes.
+
+        pf_attn checks every query token of the first and the last 32-query block and of each block in which
+        the number of key rounds changes, every eighth token elsewhere (attn_check_tokens)."""
+        c = self.cfg
+        E, F, hd, nh, nkv, L = c.n_embd, c.n_ff, c.head_dim, c.n_head, c.n_head_kv, c.n_layer
+        tokens = np.asarray(tokens, np.int64)
+        T, g = tokens.size, nh // nkv
+        assert 2 <= T <= 512, "one chunk of the batched prefill"
+        D = taps_by_layer(taps)
+        for (name, _l), v in D.items():
+            assert not name.startswith("pf_") or len(v) == 1, f"{name}: {len(v)} taps (one chunk, no int8 redo)"
+        self.kq = self.w.raw("blk.0.attn_q.weight")[1] in (TT.Q4_K, TT.Q6_K)
+        H = self.gelu_h or GELU_H[E]
+        S = attn_key_splits(hd, g)
+        data, tt, rows, cols = self.w.raw("token_embd.weight")
+        rb = data.size // rows
+        resid = np.stack([self.orc.dequantize_row(tt, data[t * rb:(t + 1) * rb], cols) for t in tokens]) \
+            * np.float32(math.sqrt(E))  # embed_tokens + scale_embeddings (model.cpp:240-344), bit-exact
+        for l in range(L):
+            t0 = T - 1 if l == L - 1 else 0  # the last layer's trim
+            Tq = T - t0
+            # 1. attn_norm rows
+            xr = self.norm_rows(resid, f"blk.{l}.attn_norm.weight").astype(np.float64)
+            self.quant_rows("pf_norm_in", D, l, "qkv", T, E, xr, NORM_RTOL * np.abs(xr).max(1, keepdims=True))
+            # 2. q/k norm, rope, q scale, K/V append
+            qkv = f32(D[("pf_qkv", l)][0]).reshape(T, (nh + 2 * nkv) * hd)
+            base = 10000.0 if self.swa(l) else c.rope_base
+            qn = self.norm_rows(qkv[:, : nh * hd].reshape(-1, hd), f"blk.{l}.attn_q_norm.weight").reshape(T, nh, hd)
+            kn = self.norm_rows(qkv[:, nh * hd:(nh + nkv) * hd].reshape(-1, hd), f"blk.{l}.attn_k_norm.weight").reshape(T, nkv, hd)
+            qr = (self.orc.rope(qn, hd, base, 1.0, pos0) * np.float32(1.0 / math.sqrt(hd))).astype(np.float64)
+            kr = self.orc.rope(kn, hd, base, 1.0, pos0).astype(np.float64)
+            v = qkv[:, (nh + nkv) * hd:].reshape(T, nkv, hd)
+            q16 = np.frombuffer(D[("pf_q", l)][0], np.float16).reshape(T, nh, hd).astype(np.float64)
+            kc = np.frombuffer(D[("kc", l)][-1], np.uint16).reshape(nkv, self.max_ctx, hd)
+            vc = np.frombuffer(D[("vc", l)][-1], np.uint16).reshape(nkv, self.max_ctx, hd)
+            k16 = kc[:, pos0:pos0 + T].view(np.float16).astype(np.float64).transpose(1, 0, 2)
+            for kind, got, ref in (("pf_qk_q", q16, qr), ("pf_qk_k", k16, kr)):
+                self.bound(kind, np.abs(got - ref), 2.0 ** -10 * np.abs(ref) + NORM_RTOL * np.abs(ref).max(-1, keepdims=True),
+                           f"layer {l} (token, head, dim)")
+            assert np.array_equal(vc[:, pos0:pos0 + T].transpose(1, 0, 2), v.astype(np.float16).view(np.uint16)), \
+                f"pf_qk_v: layer {l}: V cache rows pos0.. != f16(v)"
+            self.report["pf_qk_v"] = max(self.report["pf_qk_v"], 0.0)
+            assert not kc[:, pos0 + T:].any() and not vc[:, pos0 + T:].any(), \
+                f"pf_qk_untouched: layer {l}: a cache row past pos0 + T was written"
+            # 3. causal attention in float64 from the device's f16 q / K / V
+            sel = attn_check_tokens(T, pos0, S, t0)
+            o_ref, o_tol = self.attn_f64(q16[sel], kc, vc, pos0 + np.asarray(sel))
+            ro = np.asarray(sel) - t0
+            R = self._attn_rows(D, l, Tq, ro, nh * hd)
+            try:
+                err, bnd, qs, near = quant_errors(R, o_ref.reshape(len(sel), -1), o_tol.reshape(len(sel), -1))
+            except AssertionError as e:
+                raise AssertionError(f"pf_attn: layer {l}: {e}") from None
+            self.bound("pf_attn", err, bnd, f"layer {l} (checked query, block, element)")
+            self.report["pf_attn_rows_" + R["kind"]] = 0.0
+            # 4. post-attention norm + residual
+            o = f32(D[("pf_o", l)][0]).reshape(Tq, E)
+            ra = f32(D[("pf_resid_attn", l)][0]).reshape(Tq, E)
+            ref = resid[t0:] + self.norm_rows(o, f"blk.{l}.post_attention_norm.weight")
+            for t in range(Tq):
+                self.note("pf_resid_attn", rel_err(ra[t], ref[t].astype(np.float64)), NORM_RTOL)
+            # 5. ffn_norm rows
+            xr = self.norm_rows(ra, f"blk.{l}.ffn_norm.weight").astype(np.float64)
+            self.quant_rows("pf_norm_ffn", D, l, "gate_up", Tq, E, xr, NORM_RTOL * np.abs(xr).max(1, keepdims=True))
+            # 6. GELU(gate) * up, de-interleaved by H, bit for bit
+            gu = f32(D[("pf_gate_up", l)][0]).reshape(Tq, F // H, 2, H)
+            hid = np.stack([self.orc.gelu_mul(r[:, 0].reshape(-1), r[:, 1].reshape(-1)) for r in gu])
+            assert np.abs(hid).max() > 0, f"pf_gelu: layer {l}: the FFN is dead (GELU output all zero)"
+            self._gelu_rows(D, l, Tq, F, hid)
+            # 7. post-ffw norm + residual (before the last layer: every token)
+            dn = f32(D[("pf_down", l)][0]).reshape(Tq, E)
+            if l + 1 < L:
+                rf = f32(D[("pf_resid_ffn", l)][0]).reshape(T, E)
+                ref = ra + self.norm_rows(dn, f"blk.{l}.post_ffw_norm.weight")
+                for t in range(T):
+                    self.note("pf_resid_ffn", rel_err(rf[t], ref[t].astype(np.float64)), NORM_RTOL)
+                resid = rf
+        # 8. the tail: final residual -> output_norm -> F16 logits GEMV -> token
+        final = ra[0] + self.norm(dn[0], f"blk.{L - 1}.post_ffw_norm.weight")
+        logits = self.gemv(self.w.raw("token_embd.weight"), self.norm(final, "output_norm.weight"))
+        if ("logits", -1) in D:
+            self.note("pf_tail", rel_err(f32(D[("logits", -1)][-1]), logits.astype(np.float64)), GEMV_RTOL + 2 * NORM_RTOL)
+        if ("token", -1) in D:
+            tok = int(np.frombuffer(D[("token", -1)][-1], np.int32)[0])
+            top = np.sort(logits)[-2:]
+            if top[1] - top[0] > 1e-5 * abs(top[1]):  # decode_step's near-tie rule
+                assert tok == int(np.argmax(logits)), f"pf_tail: token {tok} vs oracle argmax {int(np.argmax(logits))}"
+
+    def attn_f64(self, q, kc, vc, qpos):
+        """Float64 causal attention of the queries q [n][heads][hd] (scaled, f16 values) at positions qpos over
+        the cache's keys 0..qpos: scores, the soft-cap c tanh(s / c) before the mask, softmax, P V; and the
+        per-element tolerance tol_i of the module docstring (pf_attn).  Returns o, tol as [n][heads][hd]."""
+        n, nh, hd = q.shape
+        nkv = kc.shape[0]
+        g, cap = nh // nkv, self.softcap
+        nk = int(qpos.max()) + 1
+        o, tol = np.zeros((n, nh, hd)), np.zeros((n, nh, hd))
+        mask = np.arange(nk)[None, :] <= qpos[:, None]
+        for h in range(nh):
+            K = kc[h // g, :nk].view(np.float16).astype(np.float64)
+            V = vc[h // g, :nk].view(np.float16).astype(np.float64)
+            s = q[:, h] @ K.T
+            if cap > 0.0:
+                s = cap * np.tanh(s / cap)
+            sm = np.where(mask, s, -np.inf)
+            e = np.exp(sm - sm.max(1, keepdims=True))
+            lsum = e.sum(1, keepdims=True)
+            p = e / lsum
+            oh = p @ V
+            es = 2.0 * math.sqrt(hd) * 2.0 ** -24 * (np.abs(q[:, h]) @ np.abs(K).T)
+            if cap > 0.0:
+                es = es + 4.0 * 2.0 ** -24 * np.abs(s)
+            sens = np.stack([((p[i] * es[i])[:, None] * np.abs(V - oh[i][None, :])).sum(0).max() for i in range(n)])
+            omax = np.abs(oh).max(1)
+            tol[:, h] = (2.0 ** -11 * (p @ np.abs(V)) + 2.0 ** -25 * (mask @ np.abs(V)) / lsum + sens[:, None]
+                         + (ATTN_F64_RTOL * np.sqrt(np.maximum(1.0, (qpos + 1) / 256.0)) * omax)[:, None])
+            o[:, h] = oh
+            self.report["pf_attn_score_sensitivity"] = max(self.report["pf_attn_score_sensitivity"],
+                                                           float((sens / np.maximum(omax, 1e-30)).max()))
+        return o, tol
+
+    def _attn_rows(self, D, l, Tq, rows, ncols):
+        """The checked rows of pf_x_o (act_rows picks the format; the attention's f16 rows carry no scale)."""
+        c = self.cfg
+        xs = max(c.n_embd, c.n_ff, c.n_head * c.head_dim) // 32
+        try:
+            R = act_rows(D, l, "o", Tq, xs, ncols, self.kq)
+        except AssertionError as e:
+            raise AssertionError(f"pf_attn: layer {l}: {e}") from None
+        return {k: (v[rows] if isinstance(v, np.ndarray) else v) for k, v in R.items()}
+
+    def _gelu_rows(self, D, l, Tq, F, hid):
+        """pf_x_down against the oracle's gelu_mul of the same gate / up floats.  NOT bit-identical on the device:
+        the prefill's GELU kernels call gelu_mul1<EXACT = false> (common.h), the device libm's tanhf rather than
+        glibc's (glibc_math.h is what is bit-checked, and only the exact engine uses it), so hid differs from the
+        oracle's in the last place now and then.  The Q8_0 blocks and f16 rows absorb that almost always (integer
+        quants, f16 d); Q8_K's f32 d = max / 127 shows it (mini-4b Q4_K, 70 tokens: the quants identical, one
+        super-block's d not).  So, as the rows of the norms: the quantisation-aware bound, every
+        element, with tol = 2^-22 max|hid| (tanhf to 2 ulp at |tanh| <= 1 through (0.5 x)(1 + t) u), and the
+        quants within 1 of the oracle's; the rows that differ in any bit are counted
+        (pf_gelu_rows_not_bit_identical)."""
+        hid64 = hid.astype(np.float64)
+        R = self.quant_rows("pf_gelu", D, l, "down", Tq, F, hid64, 2.0 ** -22 * np.abs(hid64).max(1, keepdims=True))
+        differ = 0
+        for t in range(Tq):
+            if R["kind"] == "q8_k":
+                ref = np.frombuffer(self.orc.quantize_q8_k(hid[t]), np.uint8).reshape(-1, 292)
+                w = R["words"][t]
+                # d = 1 / (-127 / max): max to tol, two f32 roundings
+                dd, dr = w[::8, 8].copy().view(np.float32).astype(np.float64), ref[:, :4].copy().view(np.float32)[:, 0].astype(np.float64)
+                self.bound("pf_gelu_q8k_d", np.abs(dd - dr), 2.0 ** -22 * np.abs(hid64[t]).max() / 127.0 + 2.0 ** -22 * np.abs(dr),
+                           f"layer {l} token {t} super-block")
+                differ += not (np.array_equal(w[:, :8].copy().view(np.int8).reshape(-1, 256), ref[:, 4:260].view(np.int8))
+                               and np.array_equal(w[::8, 8].copy().view(np.float32), ref[:, :4].copy().view(np.float32)[:, 0]))
+                continue
+            ref = self.orc.quantize_q8_0(hid[t])
+            if R["kind"] == "q8_0":
+                differ += not np.array_equal(xblocks_to_q8_0(R["words"][t]), ref)
+                continue
+            b = ref.reshape(-1, 34)
+            d = b[:, :2].copy().view(np.float16).astype(np.float32)  # f16(d) q 2^-s is exact in f32 (q8_f16_quad)
+            want = ((d * np.float32(1.0 / R["ts"][t])) * b[:, 2:].view(np.int8).astype(np.float32)).astype(np.float16)
+            differ += not np.array_equal(R["bits"][t], want.reshape(-1).view(np.uint16))
+        self.report["pf_gelu_rows_not_bit_identical"] += differ
 
     def _prefill_q8_one(self, D, l, proj, names, ncols, n_t, H):
         c = self.cfg

@@ -48,6 +48,94 @@ def _run(oracle, cfg_name, seed, n_prompt, n_decode, max_ctx, monkeypatch=None, 
     return chk
 
 
+PF_KINDS = ("pf_norm_in", "pf_qk_q", "pf_qk_k", "pf_qk_v", "pf_attn", "pf_resid_attn", "pf_norm_ffn", "pf_gelu",
+            "pf_resid_ffn", "pf_tail")
+
+
+def _run_pf(oracle, cfg_name, seed, T, pos0, max_ctx, monkeypatch=None, env=None, softcap=0.0, merge=None, **gkw):
+    """One traced single-chunk batched prefill of T tokens at pos0 (after forward() of the pos0 tokens before
+    them), its non-GEMM launches checked op by op (OpChecker.prefill_ops).  merge: whether the attention's
+    second (merge) launch must run -- the launcher's condition, asserted for the shape."""
+    from llm_inference_amd.model import Model
+    from llm_inference_amd.synthetic import CONFIGS, build_gemma3_gguf
+    from oplevel import attn_key_splits
+    cfg = CONFIGS[cfg_name]
+    g = build_gemma3_gguf(cfg, seed=seed, swa_pattern=[True, False], **gkw)
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    m = Model(g, max_ctx=max_ctx)
+    assert m.info.batched_prefill
+    chk = OpChecker(oracle, g, cfg, max_ctx, swa_pattern=[True, False], softcap=softcap)
+    prompt = np.random.default_rng(seed).integers(4, cfg.vocab, pos0 + T).astype(np.int32)
+    if pos0:
+        m.forward(prompt[:pos0], 0)
+    taps = m.trace(prompt[pos0:], pos0)
+    m.close()
+    chk.prefill_ops(taps, prompt[pos0:], pos0)
+    print(cfg_name, f"T={T} pos0={pos0}", env or "", {k: f"{v:.2e}" for k, v in sorted(chk.report.items())})
+    for k in PF_KINDS:
+        assert k in chk.report, k
+    if merge is not None:
+        S, ks = attn_key_splits(cfg.head_dim, cfg.n_head // cfg.n_head_kv), int((env or {}).get("LLMI_PREFILL_ATTN_KS", 4))
+        assert (ks > 1 and (pos0 + T - 1) // 32 + 1 > S) == merge
+    return chk
+
+
+def test_ops_prefill_nongemm_mini4b_f16(oracle):
+    """hd 256, G 2, S 2, T = 70: 3 query blocks, the last ragged (6 tokens); block 2 has 3 key tiles -> 2 rounds
+    -> 2 partials -> the merge launch, blocks 0-1 emit directly; f16 rows and token scales from the norms, the
+    attention and the GELU; the last layer's one token on the int8 path."""
+    chk = _run_pf(oracle, "mini-4b", 41, 70, 0, 128, merge=True)
+    for k in ("pf_norm_in_rows_f16", "pf_attn_rows_f16", "pf_gelu_rows_f16", "pf_attn_rows_q8_0", "pf_gelu_rows_q8_0"):
+        assert k in chk.report, k
+
+
+def test_ops_prefill_nongemm_mini4b_int8(oracle, monkeypatch):
+    """The same shape with LLMI_PREFILL_F16=0: the Q8_0 forms of the norms, the attention's emit and gelu8."""
+    chk = _run_pf(oracle, "mini-4b", 41, 70, 0, 128, monkeypatch, {"LLMI_PREFILL_F16": "0"}, merge=True)
+    assert "pf_norm_in_rows_q8_0" in chk.report and "pf_attn_rows_f16" not in chk.report
+
+
+def test_ops_prefill_nongemm_mini1b_pos530(oracle):
+    """G 4, hd 256: 37 tokens at pos0 = 530 (after a 530-token forward): 567 keys = 18 tiles, 9 rounds, 4
+    partials; split 0 runs 3 local rounds (the LDS ring half lr & 1 reused); pos0 % 32 != 0, so the diagonal
+    tile is misaligned with the query block; the G = 4 instance spills registers."""
+    _run_pf(oracle, "mini-1b", 42, 37, 530, 640, merge=True)
+
+
+def test_ops_prefill_nongemm_mini27b(oracle):
+    """hd 128, G 2, S 4, T = 45: 2 key tiles < S -- waves with sp >= n_tiles skip and merge in with m = -inf
+    and weight 0; the 27B norm width (EB = 3) and gelu16<3>."""
+    _run_pf(oracle, "mini-27b", 43, 45, 0, 64, merge=False)
+
+
+def test_ops_prefill_nongemm_mini27b_pos150(oracle):
+    """hd 128, S 4: 20 tokens at pos0 = 150: 170 keys -> 6 tiles -> 2 rounds -> 2 partials, the merge launch
+    at hd 128 (NI = 1, grid z = 4)."""
+    _run_pf(oracle, "mini-27b", 44, 20, 150, 192, merge=True)
+
+
+def test_ops_prefill_nongemm_mini4b_kquant(oracle):
+    """Q4_K layers (v and down Q6_K), centered: Q8_K blocks from the norms and the GELU against the reference's
+    quantize_row_q8_k of the true input; the attention's per-head super-block through
+    prefill_attn_merge_kernel<256, 8>."""
+    from llm_inference_amd.gguf import TensorType as TT
+    chk = _run_pf(oracle, "mini-4b", 45, 70, 0, 128, merge=True, wtype=TT.Q4_K,
+                  wtypes={"v": TT.Q6_K, "down": TT.Q6_K}, centered=True)
+    for k in ("pf_norm_in_rows_q8_k", "pf_attn_rows_q8_k", "pf_gelu_rows_q8_k"):
+        assert k in chk.report, k
+
+
+def test_ops_prefill_nongemm_mini1b_softcap(oracle):
+    """attention.logit_softcapping 20: the soft-cap branch ahead of the mask."""
+    _run_pf(oracle, "mini-1b", 46, 40, 0, 64, softcap=20.0, extra_meta={"attention.logit_softcapping": 20.0})
+
+
+def test_ops_prefill_nongemm_mini4b_one_workgroup(oracle, monkeypatch):
+    """LLMI_PREFILL_ATTN_KS=1: the single-work-group path, no partials, at the first case's shape."""
+    _run_pf(oracle, "mini-4b", 41, 70, 0, 128, monkeypatch, {"LLMI_PREFILL_ATTN_KS": "1"}, merge=False)
+
+
 def test_ops_mini4b_block(oracle):
     """Gemma-3 4B layer shapes on the attention-block path, global and local
     rope layers; prefill GEMMs of a 12-token prompt, then 3 decode steps."""
