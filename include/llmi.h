@@ -160,6 +160,26 @@ void llmi_session_destroy(llmi_session* s);
 int llmi_session_forward(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, float* logits,
                          int32_t* argmax);
 
+/* Teacher-forced scoring: runs tokens[0..n) at positions pos..pos+n-1 exactly as llmi_session_forward does
+ * (same KV rows, same session state afterwards, the last token's logits / argmax left where forward leaves
+ * them), and for EVERY position i reports, from that position's logits l_i[0..V) (after the final soft-cap):
+ *   lse[i]     = log sum_v exp(l_i[v])                      (natural log)
+ *   logprob[i] = l_i[targets[i]] - lse[i]                    (0.0f exactly where the position has no target)
+ *   argmax[i]  = first maximal index (argmax_key's rule: larger value, then smaller id)
+ * targets == NULL: targets[i] = tokens[i+1], the last position has none.  Otherwise n ids, -1 = no target.
+ * Any of logprob / lse / argmax may be NULL.  One device only (tensor-parallel session: LLMI_E_ARG).
+ * Fast sessions with a batched prefill and an F16 output table run the last layer for every token of each
+ * prefill chunk and hand the chunk's f16 final-norm rows to the fused MFMA scorer (k_score.hip: the T x V logits
+ * are never written); every other session runs the token loop with full logits and reduces each row in f64
+ * (llmi_session_info.score_path). */
+int llmi_session_score(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const int32_t* targets,
+                       float* logprob, float* lse, int32_t* argmax);
+
+/* op level, host pointers, synchronous: the fused scorer alone.  x16: [T][E] f16 bits, w16: [V][E] f16 bits
+ * (row-major), softcap <= 0: none.  E % 16 == 0, else LLMI_E_SIZE. */
+int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                    const int32_t* targets, float* logprob, float* lse, int32_t* argmax);
+
 /* Layer-by-layer triage: llmi_session_forward's token
  * loop, one token at a time with eager launches, appending the
  * intermediates the reference prints under --verbose (model.cpp VERBOSE
@@ -180,7 +200,11 @@ int llmi_session_dump(llmi_session* s, const int32_t* tokens, int n_tokens, int 
  * layer's KV cache), "ffn_resid", "ffn_norm", "hid", "down", "result_norm",
  * "logits"/"token"; the prefill taps its GEMM inputs ("pf_x_<proj>", Q8_0
  * blocks) and outputs ("pf_<proj>").  flags bit 0: the decode-loop step
- * (screened token selection) instead of forward's full logits.  Slow; the
+ * (screened token selection) instead of forward's full logits.  flags bit 1
+ * (value 2): scoring mode -- llmi_session_score's launches (targets = the next
+ * tokens), tapping per chunk "sc_x16" (the [T][E] f16 rows handed to the
+ * scorer; they carry no per-token scales, so there is no "sc_xs"), then
+ * "sc_lse", "sc_logprob" (f32) and "sc_argmax" (i32).  Slow; the
  * session's state advances exactly as llmi_session_forward's. */
 typedef void (*llmi_trace_fn)(void* user, const char* name, int layer, const void* data, size_t bytes);
 int llmi_session_trace(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, uint32_t flags,
@@ -258,8 +282,18 @@ typedef struct {
                                  (LLMI_PREFILL_F16=0, Q8_0 weights, tensor-parallel ranks), 6 f16 for K-quant layers
                                  (LLMI_PREFILL_F16=1); 0 no batched prefill */
   int sampling;               /* 1 while a sampler is set (llmi_session_set_sampler) */
+  int score_path;             /* llmi_session_score: 1 the fused MFMA scorer on the batched prefill's rows, 2 the row
+                                 path (token loop with full logits + an f64 reduce per row), 0 none (tensor parallel);
+                                 LLMI_NO_PREFILL is read at the call, as forward reads it */
 } llmi_session_info;
+/* The caller owns the struct, so the library must know how large the caller's is: fills the first
+ * min(info_size, sizeof(llmi_session_info)) bytes and never writes past info_size.  Fields are only ever appended. */
+int llmi_session_get_info_sized(const llmi_session* s, llmi_session_info* info, size_t info_size);
+/* The exported symbol of this name serves binaries built before score_path was appended: it fills the fields up to
+ * and including `sampling` (the struct as it was then, 128 bytes) and nothing after them.  Code compiled against
+ * this header reaches the sized form through the macro below and gets every field. */
 int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
+#define llmi_session_get_info(s, info) llmi_session_get_info_sized((s), (info), sizeof(llmi_session_info))
 
 /* Benchmark hook: time `reps` passes over one decode kernel family, every
  * launch with the real arguments of the decode step and bracketed by HIP
@@ -271,7 +305,9 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *   5 = qkv / o / gate_up / down as standalone layer GEMVs (round-1 family),
  *   6, 7 = the removed layer / FFN engines (always 0 / 0),
  *   8 = the sampler's two launches (candidate selection + finalize) on the session's current logits, with the
- *       session's sampler (temperature 1, top_k 64, top_p 0.95 when none is set); bytes = the logits row.
+ *       session's sampler (temperature 1, top_k 64, top_p 0.95 when none is set); bytes = the logits row;
+ *   9 = the fused scorer's launches (partials + merge) over the most recently scored chunk; bytes = the F16 table
+ *       plus the chunk's [T][E] f16 rows (0 / 0 when nothing was scored yet or the row path is in use).
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

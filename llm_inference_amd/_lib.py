@@ -53,7 +53,7 @@ class SessionInfo(C.Structure):
                 ("screened_logits", C.c_int), ("screen_bytes", C.c_size_t), ("prefill_f16_redo", C.c_int),
                 ("layer_engine", C.c_int), ("ffn_engine", C.c_int), ("tp_exchange", C.c_int),
                 ("block_slow_waits", C.c_longlong), ("exact_engine", C.c_int), ("exact_batched_prefill", C.c_int),
-                ("prefill_gemm", C.c_int), ("sampling", C.c_int)]
+                ("prefill_gemm", C.c_int), ("sampling", C.c_int), ("score_path", C.c_int)]
 
 
 SAMPLE_MAX_K = 256
@@ -94,6 +94,8 @@ _SIGS = {
     "llmi_session_peer_handle": (C.c_int, [_vp, _vp]),
     "llmi_session_peer_connect": (C.c_int, [_vp, _vp]),
     "llmi_session_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "llmi_session_score": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "llmi_score_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),
     "llmi_session_generate": (C.c_int, [_vp, _i32, C.c_int, C.c_int, _vp]),
     "llmi_session_dump": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_char_p]),
     "llmi_session_enqueue": (C.c_int, [_vp, _i32, C.c_int, C.c_int]),
@@ -101,7 +103,9 @@ _SIGS = {
     "llmi_session_sync": (C.c_int, [_vp, _vp, C.c_int]),
     "llmi_session_set_sampler": (C.c_int, [_vp, C.POINTER(Sampler)]),
     "llmi_sample_logits": (C.c_int, [_vp, _sz, C.POINTER(Sampler), C.c_int, _vp, _vp, _vp, _vp, _vp]),
-    "llmi_session_get_info": (C.c_int, [_vp, C.POINTER(SessionInfo)]),
+    # (the unsized symbol fills the struct only up to `sampling`: binaries built before score_path was appended)
+    "llmi_session_get_info": (C.c_int, [_vp, _vp]),
+    "llmi_session_get_info_sized": (C.c_int, [_vp, C.POINTER(SessionInfo), _sz]),
     "llmi_session_time_kernel": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_f64), C.POINTER(_f64)]),
     "llmi_selftest": (C.c_int, [C.c_int, _vp]),
 }

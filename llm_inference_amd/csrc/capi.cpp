@@ -3,10 +3,14 @@
 // Error contract: no C++ exception crosses the ABI; every call returns an
 // llmi_status and stores the message (the reference's own wording where it
 // has one) for llmi_last_error().
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
+#include "score_plan.h"
 #include "session.h"
 
 using namespace llmi;
@@ -429,6 +433,57 @@ int llmi_session_forward(llmi_session* s, const int32_t* tokens, int n_tokens, i
   return guard([&] { s->s->forward(tokens, n_tokens, pos, logits, argmax); });
 }
 
+int llmi_session_score(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const int32_t* targets,
+                       float* logprob, float* lse, int32_t* argmax) {
+  return guard([&] {
+    if (!s || (!tokens && n_tokens > 0)) throw status_error(LLMI_E_ARG, "score: null pointer");
+    s->s->score(tokens, n_tokens, pos, targets, logprob, lse, argmax);
+  });
+}
+
+int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                    const int32_t* targets, float* logprob, float* lse, int32_t* argmax) {
+  return guard([&] {
+    if (!x16 || !w16) throw status_error(LLMI_E_ARG, "score_rows: null pointer");
+    if (T <= 0 || V <= 0) throw status_error(LLMI_E_ARG, "score_rows: T and V must be positive");
+    if (E <= 0 || E % 16 != 0) throw status_error(LLMI_E_SIZE, "score_rows: E must be a positive multiple of 16");
+    const ScorePlan p = score_plan(T, V, E);
+    if (!p.ok) throw status_error(LLMI_E_SIZE, "score_rows: shape too large");
+    if (targets)
+      for (int i = 0; i < T; i++)
+        if (targets[i] < -1 || targets[i] >= V) throw status_error(LLMI_E_RANGE, "score_rows: target id out of range (targets)");
+    Ctx& c = ctx();
+    ScoreArgs a;
+    uint16_t* xd = (uint16_t*)c.get(0, p.x_bytes);
+    uint16_t* wd = (uint16_t*)c.get(1, p.w_bytes);
+    a.ms = (float2*)c.get(2, p.ms_bytes);
+    a.key = (unsigned long long*)c.get(3, p.key_bytes);
+    // slot 4: targets, target logits, the three outputs
+    uint8_t* misc = (uint8_t*)c.get(4, (size_t)T * 20);
+    int32_t* tg = (int32_t*)misc;
+    a.tl = (float*)(misc + (size_t)T * 4);
+    a.logprob = (float*)(misc + (size_t)T * 8);
+    a.lse = (float*)(misc + (size_t)T * 12);
+    a.argmax = (int32_t*)(misc + (size_t)T * 16);
+    LLMI_HIP(hipMemcpyAsync(xd, x16, p.x_bytes, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(wd, w16, p.w_bytes, hipMemcpyHostToDevice, c.stream));
+    if (targets) LLMI_HIP(hipMemcpyAsync(tg, targets, (size_t)T * 4, hipMemcpyHostToDevice, c.stream));
+    a.x16 = xd;
+    a.xstride = E;
+    a.w16 = wd;
+    a.T = T;
+    a.V = V;
+    a.E = E;
+    a.softcap = softcap;
+    a.targets = targets ? tg : nullptr;
+    launch_score_rows(a, c.stream);
+    if (logprob) LLMI_HIP(hipMemcpyAsync(logprob, a.logprob, (size_t)T * 4, hipMemcpyDeviceToHost, c.stream));
+    if (lse) LLMI_HIP(hipMemcpyAsync(lse, a.lse, (size_t)T * 4, hipMemcpyDeviceToHost, c.stream));
+    if (argmax) LLMI_HIP(hipMemcpyAsync(argmax, a.argmax, (size_t)T * 4, hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipStreamSynchronize(c.stream));
+  });
+}
+
 int llmi_session_dump(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const char* path) {
   return guard([&] { s->s->forward_dump(tokens, n_tokens, pos, path); });
 }
@@ -437,7 +492,7 @@ int llmi_session_trace(llmi_session* s, const int32_t* tokens, int n_tokens, int
                        llmi_trace_fn fn, void* user) {
   return guard([&] {
     if (!s || !tokens || !fn) throw status_error(LLMI_E_ARG, "null pointer");
-    s->s->forward_trace(tokens, n_tokens, pos, (flags & 1u) != 0, fn, user);
+    s->s->forward_trace(tokens, n_tokens, pos, (flags & 1u) != 0, fn, user, (flags & 2u) != 0);
   });
 }
 
@@ -554,8 +609,22 @@ int llmi_selftest(int which, unsigned long long* out) {
   });
 }
 
-int llmi_session_get_info(const llmi_session* s, llmi_session_info* info) {
-  return guard([&] { s->s->info(info); });
+int llmi_session_get_info_sized(const llmi_session* s, llmi_session_info* info, size_t info_size) {
+  return guard([&] {
+    if (!s || !info) throw status_error(LLMI_E_ARG, "get_info: null pointer");
+    llmi_session_info full;
+    std::memset(&full, 0, sizeof(full));  // padding included
+    s->s->info(&full);
+    std::memcpy(info, &full, std::min(info_size, sizeof(full)));  // never past the caller's struct
+  });
+}
+
+// The symbol binaries built before score_path was appended call, with the 128-byte struct of that header
+// (integration/main_mi355x.cpp keeps it on its stack): the fields up to `sampling` only.  The name is parenthesized
+// so that the header's macro of the same name does not expand here.
+static_assert(offsetof(llmi_session_info, score_path) == 128, "the struct's layout before score_path was appended");
+int (llmi_session_get_info)(const llmi_session* s, llmi_session_info* info) {
+  return llmi_session_get_info_sized(s, info, offsetof(llmi_session_info, score_path));
 }
 
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us, double* bytes) {

@@ -604,6 +604,54 @@ void launch_residual_norm(const float* y, const float* w_post, float* resid, con
   LLMI_HIP(hipGetLastError());
 }
 
+// residual_norm_kernel<false> (post_scale 1, w_post set) per row blockIdx.x, the same expressions and the same
+// 1024-thread sums, so row i's f16 image equals the one-row launch's NormOut::x16 bit for bit; writes nothing else
+__global__ __launch_bounds__(1024) void residual_norm_rows16_kernel(const float* __restrict__ y, int ystride,
+                                                                    const float* __restrict__ w_post,
+                                                                    const float* __restrict__ resid, int rstride,
+                                                                    const float* __restrict__ w_next,
+                                                                    uint16_t* __restrict__ x16, int xstride, int n,
+                                                                    double eps) {
+  __shared__ float sh[16];
+  const int t = threadIdx.x;
+  y += (size_t)blockIdx.x * ystride;
+  resid += (size_t)blockIdx.x * rstride;
+  x16 += (size_t)blockIdx.x * xstride;
+  float yv[NORM_EPT], rv[NORM_EPT], wp[NORM_EPT], wn[NORM_EPT];
+#pragma unroll
+  for (int k = 0; k < NORM_EPT; k++) {
+    const int i = t + k * 1024;
+    const bool ok = i < n;
+    yv[k] = ok ? y[i] : 0.0f;
+    rv[k] = ok ? resid[i] : 0.0f;
+    wp[k] = ok ? w_post[i] : 0.0f;
+    wn[k] = ok ? w_next[i] : 0.0f;
+  }
+  const float sc1 = rms_scale(sumsq_regs<false>(yv, n, nullptr, sh), n, eps);
+  float hv[NORM_EPT];
+#pragma unroll
+  for (int k = 0; k < NORM_EPT; k++) {
+    const float a = (sc1 * yv[k]) * wp[k];
+    hv[k] = rv[k] + a;
+  }
+  const float sc2 = rms_scale(sumsq_regs<false>(hv, n, nullptr, sh), n, eps);
+#pragma unroll
+  for (int k = 0; k < NORM_EPT; k++) {
+    const int i = t + k * 1024;
+    if (i < n) x16[i] = f2h_ggml((sc2 * hv[k]) * wn[k]);
+  }
+}
+
+void launch_residual_norm_rows16(const float* y, int ystride, const float* w_post, const float* resid, int rstride,
+                                 const float* w_next, uint16_t* x16, int xstride, int n, int T, double eps,
+                                 hipStream_t s) {
+  if (n > 1024 * NORM_EPT) throw std::runtime_error("residual_norm: n_embd > 8192");
+  if (T < 1 || !w_post) throw std::runtime_error("residual_norm_rows16: no rows / no post norm");
+  hipLaunchKernelGGL(residual_norm_rows16_kernel, dim3(T), dim3(1024), 0, s, y, ystride, w_post, resid, rstride, w_next,
+                     x16, xstride, n, eps);
+  LLMI_HIP(hipGetLastError());
+}
+
 // Gemma-4 per-layer inputs, second half of project_per_layer_inputs
 // (model.cpp:676-701): per layer l, nx = rms_norm(proj[l]) (ops.cpp:28-43),
 // inp[l] = (nx * nw + inp[l]) * (1 / sqrt(2)).  proj was scaled by

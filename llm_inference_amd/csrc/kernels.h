@@ -77,4 +77,33 @@ void launch_gelu_mul(const float* g, const float* u, float* o, int n, hipStream_
 void launch_dequantize_rows(uint32_t type, const uint8_t* blocks, size_t row_bytes, const int32_t* row_ids,
                             int n_ids, int n_cols, float scale, float* o, hipStream_t s);
 
+// ---- scoring (k_score.hip) ----
+// Fused scorer: per token t of x16 [T][xstride] (f16 rows of E) against the table w16 [V][E] (f16, row-major), from
+// the logits l_t[v] = x_t . w_v (f32 MFMA accumulator over all of E in k order; cap tanhf(l / cap) when
+// softcap > 0): lse[t] = log sum_v exp(l_t[v]), logprob[t] = l_t[targets[t]] - lse[t] (0.0f for target -1 or
+// targets == null), argmax[t] = the first maximal index.  The T x V logits are never written: one launch leaves
+// per (token, 128-row vocabulary tile) {max, sum exp(l - max)}, the argmax key and the target's logit, a second
+// merges each token's partials in f64 in a fixed order.  E % 16 == 0; every pointer is device memory.
+struct ScoreArgs {
+  const uint16_t* x16 = nullptr;
+  int xstride = 0;
+  const uint16_t* w16 = nullptr;
+  int T = 0, V = 0, E = 0;
+  float softcap = 0.0f;
+  const int32_t* targets = nullptr;  // [T] or null
+  // scratch (score_plan.h: ms_bytes, key_bytes, tl_bytes)
+  float2* ms = nullptr;
+  unsigned long long* key = nullptr;
+  float* tl = nullptr;
+  // outputs [T]
+  float* logprob = nullptr;
+  float* lse = nullptr;
+  int32_t* argmax = nullptr;
+};
+void launch_score_rows(const ScoreArgs& a, hipStream_t s);
+// Row path: the same three results from one f32 logits row (f64 accumulation, the same tie rule) into
+// logprob[0] / lse[0] / argmax[0]; target -1: none.
+void launch_score_reduce_row(const float* logits, int V, int target, float* logprob, float* lse, int32_t* argmax,
+                             hipStream_t s);
+
 }  // namespace llmi

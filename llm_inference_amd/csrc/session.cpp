@@ -5,6 +5,7 @@
 // and position from device memory, so a greedy decode never returns to the
 // host between tokens.
 #include "session.h"
+#include "score_plan.h"
 
 #include <cmath>
 #include <functional>
@@ -1040,7 +1041,8 @@ bool Session::prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16)
     if (f16) gather_cols(pf_x16_ + (size_t)t0 * X16, (size_t)X16 * 2, (size_t)cols * 2, T_cur_, s);
     else gather_cols(pf_xq_ + (size_t)t0 * XS, (size_t)XS * sizeof(XBlock), (size_t)(cols / 32) * sizeof(XBlock), T_cur_, s);
   };
-  const bool trim = getenv("LLMI_PREFILL_FULL_LAST") == nullptr;  // (A/B: the last layer over every token)
+  // (A/B: the last layer over every token; scoring needs every token's final row: the same arithmetic)
+  const bool trim = !score_mode_ && getenv("LLMI_PREFILL_FULL_LAST") == nullptr;
   for (int c0 = 0; c0 < n; c0 += pf_cap_) {
     const int T = std::min(pf_cap_, n - c0), p0 = pos + c0;
     T_cur_ = T;
@@ -1166,12 +1168,14 @@ bool Session::prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16)
         tap("pf_resid_ffn", l, pf_resid_, (size_t)T * E * 4, s);
       }
     }
+    if (score_mode_) score_chunk(c0, T, s);  // (before the last token's norm below updates its residual row)
     if (last_chunk) {  // the last token: final residual + output_norm -> logits (decode tail)
       NormOut o2;
       o2.xn = xn_;
       if (embd_.type == T_F16) o2.x16 = act_.x16;
       launch_residual_norm(pf_out_ + (size_t)(T - 1) * E, L_.back().post_ffw_norm, pf_resid_ + (size_t)(T - 1) * E,
                            out_norm_, o2, E, hp_.eps, false, s);
+      tap("result_norm", -1, xn_, (size_t)E * 4, s);
       record_logits(s);
     }
   }
@@ -1909,6 +1913,140 @@ void Session::forward(const int32_t* tokens, int n, int pos, float* logits, int3
   });
 }
 
+// ---- scoring (llmi_session_score) ----
+int Session::score_path() const {
+  if (tp_) return 0;
+  const bool fused = !exact_ && prefill_ok_ && getenv("LLMI_NO_PREFILL") == nullptr && embd_.type == T_F16 &&
+                     hp_.n_embd % 16 == 0 && !ple_table_.qs;
+  return fused ? 1 : 2;
+}
+
+void Session::ensure_score_buffers(int cap) {
+  if (cap <= sc_cap_) return;
+  const ScorePlan p = score_plan(cap, vocab_, hp_.n_embd);
+  if (!p.ok) throw status_error(LLMI_E_SIZE, "score: n_embd % 16 != 0");
+  // grow-only, as the prefill's chunk buffers
+  sc_x16_ = dalloc<uint16_t>(p.x_bytes / 2);
+  if (!sc_row0_) sc_row0_ = dalloc<uint16_t>((size_t)hp_.n_embd);
+  sc_tgt_ = dalloc<int32_t>((size_t)cap);
+  sc_ms_ = dalloc<float2>(p.ms_bytes / sizeof(float2));
+  sc_key_ = dalloc<unsigned long long>(p.key_bytes / 8);
+  sc_tl_ = dalloc<float>((size_t)cap);
+  sc_lp_ = dalloc<float>((size_t)cap);
+  sc_lse_ = dalloc<float>((size_t)cap);
+  sc_amax_ = dalloc<int32_t>((size_t)cap);
+  sc_cap_ = cap;
+}
+
+// Path 1, one prefill chunk (tokens c0 .. c0 + T of the call): pf_out_ holds the last layer's down rows and
+// pf_resid_ its residual rows for all T tokens.  The final residual + output_norm of every row as f16 -- the image
+// forward(tokens[:i + 1]) hands its logits GEMV -- then the fused scorer over the chunk.
+void Session::score_chunk(int c0, int T, hipStream_t s) {
+  const int E = hp_.n_embd;
+  ensure_score_buffers(pf_cap_);
+  launch_residual_norm_rows16(pf_out_, E, L_.back().post_ffw_norm, pf_resid_, E, out_norm_, sc_x16_, E, E, T, hp_.eps, s);
+  // position 0 alone is not a batched prompt: forward runs a one-token prompt as a decode step, whose row score_run
+  // left in sc_row0_
+  if (c0 == 0 && sc_row0_set_)
+    LLMI_HIP(hipMemcpyAsync(sc_x16_, sc_row0_, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
+  LLMI_HIP(hipMemcpyAsync(sc_tgt_, sc_h_tgt_.data() + c0, (size_t)T * 4, hipMemcpyHostToDevice, s));
+  tap("sc_x16", -1, sc_x16_, (size_t)T * E * 2, s);
+  ScoreArgs a;
+  a.x16 = sc_x16_;
+  a.xstride = E;
+  a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
+  a.T = T;
+  a.V = vocab_;
+  a.E = E;
+  a.softcap = hp_.final_softcap;
+  a.targets = sc_tgt_;
+  a.ms = sc_ms_;
+  a.key = sc_key_;
+  a.tl = sc_tl_;
+  a.logprob = sc_lp_;
+  a.lse = sc_lse_;
+  a.argmax = sc_amax_;
+  launch_score_rows(a, s);
+  sc_last_T_ = T;
+  tap("sc_lse", -1, sc_lse_, (size_t)T * 4, s);
+  tap("sc_logprob", -1, sc_lp_, (size_t)T * 4, s);
+  tap("sc_argmax", -1, sc_amax_, (size_t)T * 4, s);
+  LLMI_HIP(hipMemcpyAsync(sc_h_lp_.data() + c0, sc_lp_, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+  LLMI_HIP(hipMemcpyAsync(sc_h_lse_.data() + c0, sc_lse_, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+  LLMI_HIP(hipMemcpyAsync(sc_h_amax_.data() + c0, sc_amax_, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+  // (the host vectors are pageable: each copy has left the chunk's buffers when it returns)
+}
+
+// the launches of score(): sc_h_tgt_ holds the call's n resolved targets; fills sc_h_lp_ / sc_h_lse_ / sc_h_amax_
+void Session::score_run(const int32_t* tokens, int n, int pos) {
+  sc_h_lp_.assign((size_t)n, 0.0f);
+  sc_h_lse_.assign((size_t)n, 0.0f);
+  sc_h_amax_.assign((size_t)n, 0);
+  if (score_path() == 1 && n > 1) {
+    const int E = hp_.n_embd;
+    ensure_score_buffers(1);
+    sc_row0_set_ = false;
+    if (pos == 0) {  // forward(tokens[:1], 0) is a decode step: its final-norm row is position 0's
+      set_token_pos(tokens[0], 0, true);
+      if (trace_fn_) record_step(stream_, false, false, false);
+      else run_step(STEP_HIDDEN);
+      LLMI_HIP(hipMemcpyAsync(sc_row0_, act_.x16, (size_t)E * 2, hipMemcpyDeviceToDevice, stream_));
+      sc_row0_set_ = true;
+    }
+    set_token_pos(tokens[n - 1], pos + n - 1, true);  // what the token loop leaves behind
+    score_mode_ = true;
+    try {
+      prefill(tokens, n, pos);
+    } catch (...) {
+      score_mode_ = sc_row0_set_ = false;
+      throw;
+    }
+    score_mode_ = sc_row0_set_ = false;
+    return;
+  }
+  // path 2 (and a one-token call, which forward runs as a decode step on every session): the token loop with full
+  // logits, each row reduced in f64 where the step left it
+  if (!sc_lp_) {
+    sc_lp_ = dalloc<float>(std::max(sc_cap_, 1));
+    sc_lse_ = dalloc<float>(std::max(sc_cap_, 1));
+    sc_amax_ = dalloc<int32_t>(std::max(sc_cap_, 1));
+  }
+  for (int i = 0; i < n; i++) {
+    set_token_pos(tokens[i], pos + i, i == 0);
+    if (trace_fn_) record_step(stream_, false);
+    else run_step(STEP_LOGITS);
+    launch_score_reduce_row(logits_, vocab_, sc_h_tgt_[(size_t)i], sc_lp_, sc_lse_, sc_amax_, stream_);
+    tap("sc_lse", -1, sc_lse_, 4, stream_);
+    tap("sc_logprob", -1, sc_lp_, 4, stream_);
+    tap("sc_argmax", -1, sc_amax_, 4, stream_);
+    LLMI_HIP(hipMemcpyAsync(sc_h_lp_.data() + i, sc_lp_, 4, hipMemcpyDeviceToHost, stream_));
+    LLMI_HIP(hipMemcpyAsync(sc_h_lse_.data() + i, sc_lse_, 4, hipMemcpyDeviceToHost, stream_));
+    LLMI_HIP(hipMemcpyAsync(sc_h_amax_.data() + i, sc_amax_, 4, hipMemcpyDeviceToHost, stream_));
+  }
+}
+
+void Session::score(const int32_t* tokens, int n, int pos, const int32_t* targets, float* logprob, float* lse,
+                    int32_t* argmax) {
+  if (tp_) throw status_error(LLMI_E_ARG, "score: one device only (tensor-parallel session)");
+  if (n <= 0) throw status_error(LLMI_E_ARG, "score: no tokens (n_tokens)");
+  if (pos < 0 || pos + n > max_ctx_) throw status_error(LLMI_E_RANGE, "score: context overflow (pos + n_tokens)");
+  for (int i = 0; i < n; i++)
+    if (tokens[i] < 0 || tokens[i] >= vocab_) throw status_error(LLMI_E_RANGE, "score: token id out of range (tokens)");
+  sc_h_tgt_.assign((size_t)n, -1);
+  for (int i = 0; i < n; i++) {
+    const int32_t t = targets ? targets[i] : (i + 1 < n ? tokens[i + 1] : -1);
+    if (t < -1 || t >= vocab_) throw status_error(LLMI_E_RANGE, "score: target id out of range (targets)");
+    sc_h_tgt_[(size_t)i] = t;
+  }
+  ensure_usable();
+  score_run(tokens, n, pos);
+  LLMI_HIP(hipStreamSynchronize(stream_));
+  check_device_error();
+  if (logprob) std::memcpy(logprob, sc_h_lp_.data(), (size_t)n * 4);
+  if (lse) std::memcpy(lse, sc_h_lse_.data(), (size_t)n * 4);
+  if (argmax) std::memcpy(argmax, sc_h_amax_.data(), (size_t)n * 4);
+}
+
 // tensor.h print_tensor_generic for a {n, 1, 1, 1} tensor: 3 leading and 3
 // trailing values ("%12.4f") around "..., " when n > 6, then the float
 // left-to-right sum (std::accumulate) as "sum = %.6f"
@@ -1942,11 +2080,17 @@ void Session::tap(const char* name, int layer, const void* dev, size_t bytes, hi
 // llmi_session_trace: the launches of forward() (batched prefill for n > 1
 // when the session runs it, else the token loop) or of one decode-loop step
 // (gen), eager, each followed by host copies of what it produced
-void Session::forward_trace(const int32_t* tokens, int n, int pos, bool gen, llmi_trace_fn fn, void* user) {
+void Session::forward_trace(const int32_t* tokens, int n, int pos, bool gen, llmi_trace_fn fn, void* user,
+                            bool score) {
   if (n <= 0) throw status_error(LLMI_E_ARG, "trace: no tokens");
   if (pos < 0 || pos + n > max_ctx_) throw status_error(LLMI_E_RANGE, "trace: context overflow");
   for (int i = 0; i < n; i++)
     if (tokens[i] < 0 || tokens[i] >= vocab_) throw status_error(LLMI_E_RANGE, "trace: token id out of range");
+  if (score && tp_) throw status_error(LLMI_E_ARG, "trace: scoring runs on one device only (tensor-parallel session)");
+  if (score) {  // the targets of llmi_session_score(targets = NULL): the next tokens
+    sc_h_tgt_.assign((size_t)n, -1);
+    for (int i = 0; i + 1 < n; i++) sc_h_tgt_[(size_t)i] = tokens[i + 1];
+  }
   // (a tensor-parallel rank traces too -- every rank of the group must call it: the standalone exchanges run)
   const bool graph = use_graph_;
   use_graph_ = false;
@@ -1958,7 +2102,9 @@ void Session::forward_trace(const int32_t* tokens, int n, int pos, bool gen, llm
     use_graph_ = graph;
   };
   try {
-    if (n > 1 && prefill_ok_ && getenv("LLMI_NO_PREFILL") == nullptr) {
+    if (score) {
+      score_run(tokens, n, pos);
+    } else if (n > 1 && prefill_ok_ && getenv("LLMI_NO_PREFILL") == nullptr) {
       set_token_pos(tokens[n - 1], pos + n - 1, true);
       prefill(tokens, n, pos);
     } else {
@@ -2150,6 +2296,7 @@ void Session::info(llmi_session_info* o) const {
   o->kv_bytes_per_pos = kv;
   o->kernels_per_token = kernels_per_token_;
   o->sampling = sampling_ ? 1 : 0;
+  o->score_path = score_path();
 }
 
 void Session::time_kernel(int which, int reps, double* us, double* bytes) {
@@ -2176,6 +2323,45 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
     *bytes = (double)logits_w_.bytes;
     LLMI_HIP(hipMemsetAsync(amax_key_, 0, 8 * (size_t)tp_size_, stream_));
     LLMI_HIP(hipStreamSynchronize(stream_));
+    return;
+  }
+  if (which == 9) {  // the fused scorer's two launches over the most recently scored chunk (its rows are still there)
+    *us = *bytes = 0.0;
+    if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;
+    const int E = hp_.n_embd;
+    ScoreArgs a;
+    a.x16 = sc_x16_;
+    a.xstride = E;
+    a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
+    a.T = sc_last_T_;
+    a.V = vocab_;
+    a.E = E;
+    a.softcap = hp_.final_softcap;
+    a.targets = sc_tgt_;
+    a.ms = sc_ms_;
+    a.key = sc_key_;
+    a.tl = sc_tl_;
+    a.logprob = sc_lp_;
+    a.lse = sc_lse_;
+    a.argmax = sc_amax_;
+    std::vector<hipEvent_t> ev(2 * (size_t)reps);
+    for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+    LLMI_HIP(hipStreamSynchronize(stream_));
+    for (int r = 0; r < reps; r++) {
+      LLMI_HIP(hipEventRecord(ev[2 * r], stream_));
+      launch_score_rows(a, stream_);
+      LLMI_HIP(hipEventRecord(ev[2 * r + 1], stream_));
+    }
+    LLMI_HIP(hipStreamSynchronize(stream_));
+    double tot = 0;
+    for (int r = 0; r < reps; r++) {
+      float ms = 0;
+      LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
+      tot += ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    *us = tot * 1000.0 / reps;
+    *bytes = (double)vocab_ * E * 2.0 + (double)sc_last_T_ * E * 2.0;
     return;
   }
   if (which == 8) {  // the sampler's two launches on the current logits (no token feedback)

@@ -78,7 +78,11 @@ class Session {
 
   void forward(const int32_t* tokens, int n_tokens, int pos, float* logits, int32_t* argmax);
   void forward_dump(const int32_t* tokens, int n_tokens, int pos, const char* path);
-  void forward_trace(const int32_t* tokens, int n_tokens, int pos, bool gen, llmi_trace_fn fn, void* user);
+  void forward_trace(const int32_t* tokens, int n_tokens, int pos, bool gen, llmi_trace_fn fn, void* user,
+                     bool score = false);
+  // llmi_session_score
+  void score(const int32_t* tokens, int n_tokens, int pos, const int32_t* targets, float* logprob, float* lse,
+             int32_t* argmax);
   void enqueue(int32_t first, int pos, int n_steps);
   void sync(int32_t* out_tokens, int n);
   void set_sampler(const llmi_sampler* sp);  // null or temperature 0: greedy
@@ -280,6 +284,23 @@ class Session {
   float* pf_apart_ = nullptr;  // prefill attention: key-split partials
   int pf_attn_ks_ = 4;
   uint8_t* pf_gather_ = nullptr;  // tensor parallel: all-gather staging of the prefill slices
+  // scoring (llmi_session_score): path 1 = the batched prefill with the last layer over every token (prefill_run's
+  // score_mode_), each chunk's final-norm rows as f16 (sc_x16_) through the fused scorer (k_score.hip); path 2 = the
+  // token loop with full logits and launch_score_reduce_row per position
+  int score_path() const;
+  void score_run(const int32_t* tokens, int n, int pos);  // both paths, into sc_h_*
+  void score_chunk(int c0, int T, hipStream_t s);         // path 1: the chunk at token offset c0 (inside prefill_run)
+  void ensure_score_buffers(int cap);
+  bool score_mode_ = false;
+  bool sc_row0_set_ = false;  // sc_row0_ holds position 0's row as the one-token forward computes it (score_run)
+  int sc_cap_ = 0, sc_last_T_ = 0;
+  uint16_t *sc_x16_ = nullptr, *sc_row0_ = nullptr;
+  int32_t *sc_tgt_ = nullptr, *sc_amax_ = nullptr;
+  float2* sc_ms_ = nullptr;
+  unsigned long long* sc_key_ = nullptr;
+  float *sc_tl_ = nullptr, *sc_lp_ = nullptr, *sc_lse_ = nullptr;
+  std::vector<int32_t> sc_h_tgt_, sc_h_amax_;  // host: the call's resolved targets, its results
+  std::vector<float> sc_h_lp_, sc_h_lse_;
 };
 
 }  // namespace llmi

@@ -43,6 +43,12 @@ struct NormOut {
 // post_scale: Gemma-4 layer output scale, 1 = none); outputs rms(resid) * w_next
 void launch_residual_norm(const float* y, const float* w_post, float* resid, const float* w_next, const NormOut& out,
                           int n, double eps, bool exact, hipStream_t s, float post_scale = 1.0f);
+// scoring (llmi_session_score): launch_residual_norm's fast arithmetic (post_scale 1) for T rows at once, one
+// work-group per row, writing only the f16 image of rms(resid + rms(y) * w_post) * w_next -- bit for bit what the
+// one-row launch hands the logits GEMV as NormOut::x16; resid is left as it is
+void launch_residual_norm_rows16(const float* y, int ystride, const float* w_post, const float* resid, int rstride,
+                                 const float* w_next, uint16_t* x16, int xstride, int n, int T, double eps,
+                                 hipStream_t s);
 // Gemma-4 per-layer inputs (model.cpp:676-701): inp[l][i] = (rms(proj[l])[i] * nw[i] + inp[l][i]) / sqrt(2),
 // proj already scaled by 1/sqrt(n_embd); one work-group per layer
 void launch_ple_combine(const float* proj, const float* nw, float* inp, int n_layer, int n_epl, double eps, bool exact,

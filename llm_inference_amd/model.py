@@ -16,6 +16,7 @@ import numpy as np
 from ._lib import (LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, TP_ID_BYTES, TRACE_FN, Sampler,
                    SessionInfo, SessionOpts, check, lib, ptr)
 from .gguf import GGUFFile
+from .score import ScoreResult, resolve_targets
 
 
 def tp_unique_id() -> bytes:
@@ -80,7 +81,7 @@ class Model:
 
     def get_info(self) -> SessionInfo:
         info = SessionInfo()
-        check(lib().llmi_session_get_info(self.h, C.byref(info)))
+        check(lib().llmi_session_get_info_sized(self.h, C.byref(info), C.sizeof(info)))
         return info
 
     def forward(self, tokens: Sequence[int], pos: int, want_logits: bool = True):
@@ -97,9 +98,27 @@ class Model:
         t = np.ascontiguousarray(tokens, np.int32)
         check(lib().llmi_session_dump(self.h, ptr(t), t.size, pos, path.encode()))
 
-    def trace(self, tokens: Sequence[int], pos: int, gen: bool = False) -> list:
+    def score(self, tokens: Sequence[int], pos: int = 0, targets: Optional[Sequence[int]] = None) -> ScoreResult:
+        """llmi_session_score: run the tokens as forward() does and return, for every position, the log-prob of
+        its target (default: the next token; -1 = none), the log-sum-exp of its logits and its greedy id
+        (.logprobs / .lse / .argmax, and .nll / .perplexity over the positions with a target)."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        tg = None if targets is None else np.ascontiguousarray(targets, np.int32)
+        if tg is not None and tg.shape != t.shape:
+            raise ValueError("targets must have one id per token (-1: no target)")
+        lp, lse, am = np.zeros(t.size, np.float32), np.zeros(t.size, np.float32), np.zeros(t.size, np.int32)
+        check(lib().llmi_session_score(self.h, ptr(t), t.size, pos, ptr(tg) if tg is not None else None,
+                                       ptr(lp), ptr(lse), ptr(am)))
+        self.last_argmax = int(am[-1])
+        return ScoreResult(lp, lse, am, resolve_targets(t, tg))
+
+    def perplexity(self, tokens: Sequence[int]) -> float:
+        """exp(nll / count) of the tokens after the first, each scored given the ones before it."""
+        return self.score(tokens).perplexity
+
+    def trace(self, tokens: Sequence[int], pos: int, gen: bool = False, score: bool = False) -> list:
         """llmi_session_trace: run the launches forward() (or, gen=True, one
-        decode-loop step) performs, eagerly, and return what each launch
+        decode-loop step; score=True: score()) performs, eagerly, and return what each launch
         produced as [(name, layer, bytes)] in launch order (op-level parity
         tests compare each against the oracle from the device's own inputs)."""
         t = np.ascontiguousarray(tokens, np.int32)
@@ -109,7 +128,7 @@ class Model:
             out.append((name.decode(), int(layer), C.string_at(data, nbytes)))
 
         fn = TRACE_FN(cb)  # kept alive for the duration of the call
-        check(lib().llmi_session_trace(self.h, ptr(t), t.size, pos, 1 if gen else 0, fn, None))
+        check(lib().llmi_session_trace(self.h, ptr(t), t.size, pos, (1 if gen else 0) | (2 if score else 0), fn, None))
         return out
 
     def set_sampler(self, sampler: Optional[dict] = None, *, temperature: Optional[float] = None, top_k: int = 0,

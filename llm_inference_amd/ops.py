@@ -192,6 +192,32 @@ def sample_logits(logits, pos: int, temperature: float, top_k: int = 0, top_p: f
     return int(tok[0]), cand[:nc.value].copy(), cq[:nc.value].copy(), nn.value
 
 
+def _f16_bits(a) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype == np.uint16:
+        return np.ascontiguousarray(a)
+    return np.ascontiguousarray(a.astype(np.float16)).view(np.uint16)
+
+
+def score_rows(x16, w16, targets=None, softcap: float = 0.0):
+    """llmi_score_rows: the fused scorer alone.  x16 [T][E] and w16 [V][E] as float16 (or
+    their uint16 bits); per row t of x16, from the logits x16[t] . w16[v] (after cap tanh(l / cap) when softcap > 0):
+    the log-prob of targets[t] (0.0 for -1 or targets None), the log-sum-exp and the first-index argmax, as a
+    ScoreResult.  E % 16 != 0 raises (LLMI_E_SIZE)."""
+    from .score import ScoreResult
+    x, w = _f16_bits(x16), _f16_bits(w16)
+    if x.ndim != 2 or w.ndim != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError("score_rows: x16 [T][E] and w16 [V][E]")
+    T, E = x.shape
+    tg = None if targets is None else np.ascontiguousarray(targets, np.int32)
+    if tg is not None and tg.shape != (T,):
+        raise ValueError("score_rows: one target per row (-1: none)")
+    lp, lse, am = np.zeros(T, np.float32), np.zeros(T, np.float32), np.zeros(T, np.int32)
+    check(lib().llmi_score_rows(ptr(x), ptr(w), T, w.shape[0], E, float(softcap), ptr(tg) if tg is not None else None,
+                                ptr(lp), ptr(lse), ptr(am)))
+    return ScoreResult(lp, lse, am, tg if tg is not None else np.full(T, -1, np.int32))
+
+
 class DeviceWeight:
     """A GGUF weight uploaded once (llmi_weight_create); multiply many times."""
 
