@@ -175,6 +175,35 @@ int llmi_session_forward(llmi_session* s, const int32_t* tokens, int n_tokens, i
 int llmi_session_score(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const int32_t* targets,
                        float* logprob, float* lse, int32_t* argmax);
 
+/* Several sequences per step.  Fast sessions on one device with a batched prefill, the fused
+ * scorer (F16 output table), Gemma-3 layers of Q4_0 / Q8_0 weights (no K-quant layers) and head_dim 128 or 256 only;
+ * every other session gets LLMI_E_ARG from seq_reserve, the message naming the reason.
+ * Row contract: if K/V rows 0..p-1 of a slot were written by the batched prefill or by
+ * batch steps for tokens x[0..p), a batch step running x[p] at position p of that slot gives, bit for bit, the last
+ * position of llmi_session_score / llmi_session_forward of x[0..p] on a fresh session -- whatever B, the other rows,
+ * the slot and the row order.  (Rows written by the one-token decode graph -- forward with one token, generate --
+ * carry that path's roundings: continuing from them works, nothing bit-exact is promised.) */
+#define LLMI_SEQ_MAX 64
+/* KV slots 0..n_seq-1.  Slot 0 IS the session's own cache (forward / generate / score keep using it, their graphs
+ * untouched); slots 1.. are allocated here, same [n_head_kv][max_ctx][head_dim] f16 layout per layer.  May be
+ * called again with a larger n_seq (existing slots keep their rows).  1 <= n_seq <= LLMI_SEQ_MAX. */
+int llmi_session_seq_reserve(llmi_session* s, int n_seq);
+/* K/V rows [0, n_pos) of every layer, slot src -> slot dst (a prompt run by forward() lands in slot 0; this moves
+ * or forks it).  Ordered on the session's stream. */
+int llmi_session_seq_copy(llmi_session* s, int dst, int src, int n_pos);
+/* One step for B rows: row b runs token tokens[b] at position pos[b] of slot slots[b] (appends its K/V there,
+ * attends keys 0..pos[b] of that slot).  argmax[b] / lse[b] (may be NULL) come from the fused scorer; logits
+ * ([B][vocab], may be NULL) from the F16 logits GEMV row by row (slow: one table read per row; for host-side
+ * sampling).  Slots must be distinct within a call.  1 <= B <= n_seq. */
+int llmi_session_batch_forward(llmi_session* s, const int32_t* tokens, const int32_t* slots, const int32_t* pos,
+                               int B, float* logits, int32_t* argmax, float* lse);
+/* Greedy loop on the device, no host round trip between steps: step i feeds row b's arg-max back as its next token
+ * at pos[b] + i + 1.  out[i * B + b] = row b's id after step i.  stop (n_stop <= 4 ids, may be NULL): once row b
+ * emits one, that entry is the stop id, every later entry of row b is -1, and row b appends nothing at or past
+ * the position the stop id would have taken (main.cpp:196's break, per row).  pos[b] + n_steps <= max_ctx. */
+int llmi_session_batch_generate(llmi_session* s, const int32_t* first, const int32_t* slots, const int32_t* pos,
+                                int B, int n_steps, const int32_t* stop, int n_stop, int32_t* out);
+
 /* op level, host pointers, synchronous: the fused scorer alone.  x16: [T][E] f16 bits, w16: [V][E] f16 bits
  * (row-major), softcap <= 0: none.  E % 16 == 0, else LLMI_E_SIZE. */
 int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
@@ -282,10 +311,17 @@ typedef struct {
                                  (LLMI_PREFILL_F16=0, Q8_0 weights, tensor-parallel ranks), 6 f16 for K-quant layers
                                  (LLMI_PREFILL_F16=1); 0 no batched prefill */
   int sampling;               /* 1 while a sampler is set (llmi_session_set_sampler) */
+  /* (bytes 132..135, the tail padding after score_path, carry the KV slot count: LLMI_SESSION_INFO_N_SEQ below.
+   *  The next field appended goes there as `int n_seq`, not after them.) */
   int score_path;             /* llmi_session_score: 1 the fused MFMA scorer on the batched prefill's rows, 2 the row
                                  path (token loop with full logits + an f64 reduce per row), 0 none (tensor parallel);
                                  LLMI_NO_PREFILL is read at the call, as forward reads it */
 } llmi_session_info;
+/* The KV slot count (llmi_session_seq_reserve; 1 until reserved) travels in the four bytes after score_path -- the
+ * struct's tail padding, so sizeof stays 136 and score_path stays the last declared field.  llmi_session_get_info_sized
+ * writes it when info_size covers those bytes; read it with this macro (info: a llmi_session_info*). */
+#define LLMI_SESSION_INFO_N_SEQ_OFFSET 132
+#define LLMI_SESSION_INFO_N_SEQ(info) (*(const int*)((const char*)(info) + LLMI_SESSION_INFO_N_SEQ_OFFSET))
 /* The caller owns the struct, so the library must know how large the caller's is: fills the first
  * min(info_size, sizeof(llmi_session_info)) bytes and never writes past info_size.  Fields are only ever appended. */
 int llmi_session_get_info_sized(const llmi_session* s, llmi_session_info* info, size_t info_size);
@@ -307,7 +343,10 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *   8 = the sampler's two launches (candidate selection + finalize) on the session's current logits, with the
  *       session's sampler (temperature 1, top_k 64, top_p 0.95 when none is set); bytes = the logits row;
  *   9 = the fused scorer's launches (partials + merge) over the most recently scored chunk; bytes = the F16 table
- *       plus the chunk's [T][E] f16 rows (0 / 0 when nothing was scored yet or the row path is in use).
+ *       plus the chunk's [T][E] f16 rows (0 / 0 when nothing was scored yet or the row path is in use);
+ *  10 = the multi-sequence attention launch (+ its merge) of the most recent batch step, one pass over the layers;
+ *       bytes = the K and V rows 0..pos[b] of every row that was live in that step, per layer (0 / 0 before any
+ *       batch step).
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

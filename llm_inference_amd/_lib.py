@@ -55,8 +55,15 @@ class SessionInfo(C.Structure):
                 ("block_slow_waits", C.c_longlong), ("exact_engine", C.c_int), ("exact_batched_prefill", C.c_int),
                 ("prefill_gemm", C.c_int), ("sampling", C.c_int), ("score_path", C.c_int)]
 
+    @property
+    def n_seq(self) -> int:
+        """KV slots (llmi_session_seq_reserve; 1 until reserved): the four bytes after score_path, the struct's
+        tail padding (include/llmi.h LLMI_SESSION_INFO_N_SEQ)."""
+        return C.c_int.from_address(C.addressof(self) + 132).value
+
 
 SAMPLE_MAX_K = 256
+SEQ_MAX = 64  # LLMI_SEQ_MAX: KV slots of one session
 
 
 class Sampler(C.Structure):
@@ -95,6 +102,10 @@ _SIGS = {
     "llmi_session_peer_connect": (C.c_int, [_vp, _vp]),
     "llmi_session_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "llmi_session_score": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "llmi_session_seq_reserve": (C.c_int, [_vp, C.c_int]),
+    "llmi_session_seq_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
+    "llmi_session_batch_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "llmi_session_batch_generate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "llmi_score_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),
     "llmi_session_generate": (C.c_int, [_vp, _i32, C.c_int, C.c_int, _vp]),
     "llmi_session_dump": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_char_p]),

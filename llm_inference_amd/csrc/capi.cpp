@@ -441,6 +441,36 @@ int llmi_session_score(llmi_session* s, const int32_t* tokens, int n_tokens, int
   });
 }
 
+int llmi_session_seq_reserve(llmi_session* s, int n_seq) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "seq_reserve: null pointer");
+    s->s->seq_reserve(n_seq);
+  });
+}
+
+int llmi_session_seq_copy(llmi_session* s, int dst, int src, int n_pos) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "seq_copy: null pointer");
+    s->s->seq_copy(dst, src, n_pos);
+  });
+}
+
+int llmi_session_batch_forward(llmi_session* s, const int32_t* tokens, const int32_t* slots, const int32_t* pos,
+                               int B, float* logits, int32_t* argmax, float* lse) {
+  return guard([&] {
+    if (!s || !tokens || !slots || !pos) throw status_error(LLMI_E_ARG, "batch_forward: null pointer");
+    s->s->batch_forward(tokens, slots, pos, B, logits, argmax, lse);
+  });
+}
+
+int llmi_session_batch_generate(llmi_session* s, const int32_t* first, const int32_t* slots, const int32_t* pos,
+                                int B, int n_steps, const int32_t* stop, int n_stop, int32_t* out) {
+  return guard([&] {
+    if (!s || !first || !slots || !pos || (!out && n_steps > 0)) throw status_error(LLMI_E_ARG, "batch_generate: null pointer");
+    s->s->batch_generate(first, slots, pos, B, n_steps, stop, n_stop, out);
+  });
+}
+
 int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
                     const int32_t* targets, float* logprob, float* lse, int32_t* argmax) {
   return guard([&] {
@@ -615,6 +645,12 @@ int llmi_session_get_info_sized(const llmi_session* s, llmi_session_info* info, 
     llmi_session_info full;
     std::memset(&full, 0, sizeof(full));  // padding included
     s->s->info(&full);
+    // the KV slot count in the four bytes after score_path (the tail padding: LLMI_SESSION_INFO_N_SEQ)
+    static_assert(sizeof(llmi_session_info) == LLMI_SESSION_INFO_N_SEQ_OFFSET + sizeof(int) &&
+                      offsetof(llmi_session_info, score_path) + sizeof(int) == LLMI_SESSION_INFO_N_SEQ_OFFSET,
+                  "n_seq lies in llmi_session_info's tail padding");
+    const int n_seq = s->s->n_seq();
+    std::memcpy(reinterpret_cast<char*>(&full) + LLMI_SESSION_INFO_N_SEQ_OFFSET, &n_seq, sizeof(int));
     std::memcpy(info, &full, std::min(info_size, sizeof(full)));  // never past the caller's struct
   });
 }

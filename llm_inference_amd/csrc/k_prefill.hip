@@ -1152,12 +1152,21 @@ __global__ __launch_bounds__(64 * WR * WT, OCC) void prefill_gemm7_kernel(Prefil
 // ---------------------------------------------------------------------------
 // q/k norm + rope (+ q scale) and the K/V cache append, one wave per row
 // ---------------------------------------------------------------------------
-template <int HD>
+// MS: the multi-sequence form (PrefillQK::rows) -- the token row's own position and slot; the arithmetic is the same
+template <int HD, bool MS = false>
 __global__ __launch_bounds__(64) void prefill_qk_kernel(PrefillQK a) {
   constexpr int DPL = HD >= 64 ? HD / 64 : 1;
   constexpr int PX = HD >= 64 ? 32 : HD / 2;
   const int lane = threadIdx.x, tok = blockIdx.x, row = blockIdx.y;
-  const int pos = a.pos0 + tok;
+  int pos = a.pos0 + tok;
+  uint16_t *kc = a.k_cache, *vc = a.v_cache;
+  if constexpr (MS) {
+    const SeqRow sr = a.rows[tok];
+    if (sr.pos < 0) return;  // an ended row of the greedy loop: nothing appended (its q row is never read)
+    pos = sr.pos;
+    kc = a.kv_tab[2 * sr.slot];
+    vc = a.kv_tab[2 * sr.slot + 1];
+  }
   const float* qkv = a.qkv + (size_t)tok * a.qkv_stride;
   const bool ok = lane * DPL < HD;
   const int nq = a.n_head, nkv = a.n_head_kv;
@@ -1166,7 +1175,7 @@ __global__ __launch_bounds__(64) void prefill_qk_kernel(PrefillQK a) {
 #pragma unroll
     for (int d = 0; d < DPL; d++) {
       const int i = lane * DPL + d;
-      if (ok) a.v_cache[((size_t)kvh * a.max_ctx + pos) * HD + i] = f2h_ggml(qkv[a.v_off + kvh * HD + i]);
+      if (ok) vc[((size_t)kvh * a.max_ctx + pos) * HD + i] = f2h_ggml(qkv[a.v_off + kvh * HD + i]);
     }
     return;
   }
@@ -1196,7 +1205,7 @@ __global__ __launch_bounds__(64) void prefill_qk_kernel(PrefillQK a) {
     if (is_q)
       a.q_out[((size_t)tok * nq + row) * HD + i] = f2h_ggml(o * a.attn_scale);
     else
-      a.k_cache[((size_t)(row - nq) * a.max_ctx + pos) * HD + i] = f2h_ggml(o);
+      kc[((size_t)(row - nq) * a.max_ctx + pos) * HD + i] = f2h_ggml(o);
   }
 }
 
@@ -1486,7 +1495,10 @@ __device__ __forceinline__ void attn_emit(const PrefillAttn& a, const v16f (&o)[
   }
 }
 
-template <int HD, int G, int S>
+// MS: the multi-sequence decode form (PrefillAttn::rows): grid.y counts rows, not query blocks -- row b is the
+// single-sequence launch's T = 1 at pos0 = rows[b].pos on its slot's caches, instruction for instruction (lane r of
+// the 32 query columns holds the one query again; only column 0 is merged into a partial or emitted)
+template <int HD, int G, int S, bool MS = false>
 __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAttn a, int T) {
   constexpr int U = HD / 8;                // 16-B units per cache row
   constexpr int SWM = U < 16 ? U - 1 : 15;  // swizzle mask (units)
@@ -1502,11 +1514,23 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, h = lane >> 5;
   const int g = w % G, sp = w / G;
   // heaviest (last) query blocks first: dispatch order is a speed matter only
-  const int hk = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y, tok0 = qb * 32, hq = hk * G + g;
-  const int qtok = min(tok0 + r, T - 1);
-  const int qpos = a.pos0 + tok0 + r;                       // this lane's query position
-  const int last_pos = a.pos0 + min(tok0 + 32, T) - 1;     // the block's last query
-  const int first_pos = a.pos0 + tok0;
+  const int hk = blockIdx.x, qb = MS ? blockIdx.y : gridDim.y - 1 - blockIdx.y, hq = hk * G + g;
+  int tok0 = qb * 32, pos0 = a.pos0, otok0 = tok0;  // otok0: the token row of query column 0
+  const uint16_t *kc = a.k_cache, *vc = a.v_cache;
+  if constexpr (MS) {
+    const SeqRow sr = a.rows[qb];
+    if (sr.pos < 0) return;  // an ended row: whole work-group, before any barrier
+    T = 1;
+    tok0 = 0;
+    otok0 = qb;
+    pos0 = sr.pos;
+    kc = a.kv_tab[2 * sr.slot];
+    vc = a.kv_tab[2 * sr.slot + 1];
+  }
+  const int qtok = MS ? qb : min(tok0 + r, T - 1);
+  const int qpos = pos0 + tok0 + r;                       // this lane's query position
+  const int last_pos = pos0 + min(tok0 + 32, T) - 1;     // the block's last query
+  const int first_pos = pos0 + tok0;
   const int n_tiles = last_pos / 32 + 1, n_rounds = (n_tiles + S - 1) / S;
   // key splits across work-groups: round q (tiles S q .. S q + S - 1) is work-group q % KS's (blockIdx.z) -- a
   // function of the key position only, so chunk-exact and the same on tensor-parallel ranks; a query block with
@@ -1525,7 +1549,7 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
       const int kind = q / (TILE / 1024), pp = q % (TILE / 1024);
       const int row = pp * RPP + lane / U, slot = lane % U, u = slot ^ (row & SWM);
       const int key = min(32 * (S * round + j) + row, a.max_ctx - 1);
-      const uint16_t* src = (kind ? a.v_cache : a.k_cache) + (cache0 + key) * HD + u * 8;
+      const uint16_t* src = (kind ? vc : kc) + (cache0 + key) * HD + u * 8;
       glds16(src, tile_ptr(lr, j) + kind * TILE + pp * 1024);
     }
   };
@@ -1641,6 +1665,7 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
   }
   if (nks > 1) {  // this work-group's partial (m, l, O^T); prefill_attn_merge_kernel combines them
     float* pp = a.part + (((size_t)hq * gridDim.y + qb) * KS + ks) * (64 * (HD / 2 + 2));
+    if (MS && r != 0) return;  // one query: columns 1.. repeat it and the merge never reads them
     pp[lane] = m_run;
     pp[64 + lane] = l_run;
 #pragma unroll
@@ -1653,7 +1678,7 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
   }
   // O = O^T / l -> Q8_0 blocks (32 head dims = one tile column; lanes q and q + 32 hold 16 each), or f16
   if (tok0 + r >= T) return;  // after the last LDS read: the partner lane of a live query is also out
-  attn_emit<HD, HD / 32>(a, o, l_run, 0, tok0 + r, hq, h);
+  attn_emit<HD, HD / 32>(a, o, l_run, 0, otok0 + r, hq, h);
 }
 
 // Key-split partials of the query blocks that have more than one (prefill_attn_mfma_kernel, a.ks > 1): one wave
@@ -1661,11 +1686,20 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
 // head) -- rescales every partial against their maximum and sums them in split order, then writes the outputs
 // as the attention kernel does.  Spread over the chip: the partials of one query block are read by HD / 32
 // work-groups at once rather than by the one work-group that counted in last (round 3, first cut: 26.8 us).
-template <int HD, int NI>
+template <int HD, int NI, bool MS = false>
 __global__ __launch_bounds__(64) void prefill_attn_merge_kernel(PrefillAttn a, int T, int S) {
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int hq = blockIdx.x, nqb = gridDim.y, qb = nqb - 1 - blockIdx.y, tok0 = qb * 32, i0 = blockIdx.z * NI;
-  const int last_pos = a.pos0 + min(tok0 + 32, T) - 1;
+  const int hq = blockIdx.x, nqb = gridDim.y, qb = MS ? blockIdx.y : nqb - 1 - blockIdx.y, i0 = blockIdx.z * NI;
+  int tok0 = qb * 32, pos0 = a.pos0, otok0 = tok0;
+  if constexpr (MS) {  // row qb's one query (prefill_attn_mfma_kernel<.., MS>): lanes 0 and 32 hold it
+    const SeqRow sr = a.rows[qb];
+    if (sr.pos < 0 || r != 0) return;
+    T = 1;
+    tok0 = 0;
+    otok0 = qb;
+    pos0 = sr.pos;
+  }
+  const int last_pos = pos0 + min(tok0 + 32, T) - 1;
   const int n_rounds = (last_pos / 32 + 1 + S - 1) / S, KS = a.ks, nks = min(KS, n_rounds);
   if (nks <= 1) return;  // written by the attention kernel
   constexpr int SLAB = 64 * (HD / 2 + 2);
@@ -1716,7 +1750,7 @@ __global__ __launch_bounds__(64) void prefill_attn_merge_kernel(PrefillAttn a, i
         }
     }
   if (tok0 + r >= T) return;
-  attn_emit<HD, NI>(a, o, l, i0, tok0 + r, hq, h);
+  attn_emit<HD, NI>(a, o, l, i0, otok0 + r, hq, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -1992,6 +2026,16 @@ void launch_prefill_gemm(const DevWeight& w, const XBlock* x, int xstride, int T
 
 void launch_prefill_qk(const PrefillQK& a, int T, hipStream_t s) {
   const dim3 grid(T, a.n_head + 2 * a.n_head_kv);
+  if (a.rows) {  // multi-sequence rows
+    if (!a.kv_tab) throw std::runtime_error("prefill_qk: multi-sequence rows need the slot table");
+    switch (a.head_dim) {
+      case 128: hipLaunchKernelGGL((prefill_qk_kernel<128, true>), grid, dim3(64), 0, s, a); break;
+      case 256: hipLaunchKernelGGL((prefill_qk_kernel<256, true>), grid, dim3(64), 0, s, a); break;
+      default: throw std::runtime_error("prefill_qk: the multi-sequence form needs head_dim 128 or 256");
+    }
+    LLMI_HIP(hipGetLastError());
+    return;
+  }
   switch (a.head_dim) {
     case 64: hipLaunchKernelGGL(prefill_qk_kernel<64>, grid, dim3(64), 0, s, a); break;
     case 128: hipLaunchKernelGGL(prefill_qk_kernel<128>, grid, dim3(64), 0, s, a); break;
@@ -2001,8 +2045,47 @@ void launch_prefill_qk(const PrefillQK& a, int T, hipStream_t s) {
   LLMI_HIP(hipGetLastError());
 }
 
+// The MFMA attention launch for GQA group G, single-sequence (MS false) or multi-sequence form: ONE table of the
+// key splits per work-group for both, so a batch row cannot merge other splits than the single-sequence launch
+// (the row contract).  S (LDS: two rounds of S tiles, and the merge) depends on head_dim only
+// but for G = 4 at head_dim 128, so a tensor-parallel rank (fewer heads per kv head: smaller G) merges the same
+// splits as the whole model (bit-identical).  head_dim 256 at G 1 / 4 spills some of the 128 O^T + 64 Q^T registers
+// (correct, slower).  Returns S, 0 for a group it does not cover.
+template <int HD, bool MS>
+static int launch_attn_mfma(const PrefillAttn& a, int T, const dim3& grid, hipStream_t s) {
+  constexpr int S4 = HD >= 256 ? 2 : 4;
+  constexpr int SG4 = HD == 128 ? 2 : S4;
+  switch (a.n_head / a.n_head_kv) {
+    case 1: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 1, S4, MS>), grid, dim3(64 * S4), 0, s, a, T); return S4;
+    case 2: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 2, S4, MS>), grid, dim3(128 * S4), 0, s, a, T); return S4;
+    case 4: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 4, SG4, MS>), grid, dim3(256 * SG4), 0, s, a, T); return SG4;
+    default: return 0;
+  }
+}
+
+// The multi-sequence decode form: T rows, one query each.  Grid (kv head, row, key split): the key splits are sized
+// by a.ks as the single-sequence launch's are, and a row with fewer rounds than ks leaves its spare work-groups
+// before any barrier (as a short query block does there).  The merge runs when a.pos0 -- here the LONGEST row's
+// position, a host-side bound -- has more than one partial; each row's merge work-groups decide for themselves.
+// head_dim 128 / 256 (the sizes the tests cover), Q8_0 or f16 outputs.
+template <int HD>
+static void attn_rows(const PrefillAttn& a, int T, hipStream_t s) {
+  if constexpr (HD < 128) {
+    throw std::runtime_error("prefill_attn: the multi-sequence form needs head_dim 128 or 256");
+  } else {
+    if (!a.kv_tab || getenv("LLMI_PREFILL_ATTN_V1") || a.q8k || !a.part || a.ks < 1 || a.ks > PREFILL_ATTN_KS_MAX)
+      throw std::runtime_error("prefill_attn: the multi-sequence form needs the MFMA kernel, Q8_0 / f16 outputs and "
+                               "the partial scratch");
+    const int S = launch_attn_mfma<HD, true>(a, T, dim3(a.n_head_kv, T, a.ks), s);
+    if (!S) throw std::runtime_error("prefill_attn: the multi-sequence form needs GQA group 1, 2 or 4");
+    if (a.ks > 1 && a.pos0 / 32 + 1 > S)
+      hipLaunchKernelGGL((prefill_attn_merge_kernel<HD, 1, true>), dim3(a.n_head, T, HD / 32), dim3(64), 0, s, a, T, S);
+  }
+}
+
 template <int HD>
 static void attn_g(const PrefillAttn& a, int T, hipStream_t s) {
+  if (a.rows) return attn_rows<HD>(a, T, s);
   const int G = a.n_head / a.n_head_kv;
   if ((a.x16 || a.q8k) && (getenv("LLMI_PREFILL_ATTN_V1") || (G != 1 && G != 2 && G != 4)))
     throw std::runtime_error("prefill_attn: f16 / Q8_K output needs the MFMA kernel (GQA group 1, 2 or 4)");
@@ -2010,22 +2093,7 @@ static void attn_g(const PrefillAttn& a, int T, hipStream_t s) {
   if (!getenv("LLMI_PREFILL_ATTN_V1") && HD >= 64) {
     if (a.ks > 1 && (!a.part || a.ks > PREFILL_ATTN_KS_MAX))
       throw std::runtime_error("prefill_attn: key splits need the partial scratch");
-    const dim3 grid(a.n_head_kv, (T + 31) / 32, std::max(1, a.ks));
-    // key splits per work-group (LDS: two rounds of S tiles, and the merge); S depends on head_dim only, so a
-    // tensor-parallel rank (fewer heads per kv head: smaller G) merges the same splits as the whole model
-    // (bit-identical).  head_dim 256 at G 1 / 4 spills some of the 128 O^T + 64 Q^T registers (correct, slower).
-    constexpr int S4 = HD >= 256 ? 2 : 4;
-    int S = 0;
-    switch (G) {
-      case 1: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 1, S4>), grid, dim3(64 * S4), 0, s, a, T); S = S4; break;
-      case 2: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 2, S4>), grid, dim3(128 * S4), 0, s, a, T); S = S4; break;
-      case 4:
-        hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 4, HD == 128 ? 2 : S4>), grid, dim3(256 * (HD == 128 ? 2 : S4)),
-                           0, s, a, T);
-        S = HD == 128 ? 2 : S4;
-        break;
-      default: break;
-    }
+    const int S = launch_attn_mfma<HD, false>(a, T, dim3(a.n_head_kv, (T + 31) / 32, std::max(1, a.ks)), s);
     if (S) {
       const int nqb = (T + 31) / 32;
       if (a.ks > 1 && (a.pos0 + T - 1) / 32 + 1 > S) {  // some query block has more than one partial
@@ -2056,6 +2124,36 @@ void launch_prefill_attn(const PrefillAttn& a, int T, hipStream_t s) {
     case 256: attn_g<256>(a, T, s); break;
     default: throw std::runtime_error("prefill_attn: head_dim");
   }
+  LLMI_HIP(hipGetLastError());
+}
+
+// the greedy batch loop's feedback (session_kernels.h): one lane per row, plain vector stores
+__global__ __launch_bounds__(64) void batch_feedback_kernel(const int32_t* __restrict__ argmax, SeqRow* __restrict__ rows,
+                                                            int32_t* __restrict__ tokens, int B, BatchStops stops,
+                                                            int32_t* __restrict__ out) {
+  const int b = threadIdx.x;
+  if (b >= B) return;
+  const SeqRow sr = rows[b];
+  if (sr.pos < 0) {
+    out[b] = -1;
+    return;
+  }
+  const int32_t id = argmax[b];
+  out[b] = id;
+  bool stop = false;
+  for (int i = 0; i < 4; i++) stop = stop || (i < stops.n && stops.id[i] == id);
+  if (stop) {
+    rows[b].pos = -1;
+  } else {
+    tokens[b] = id;
+    rows[b].pos = sr.pos + 1;
+  }
+}
+
+void launch_batch_feedback(const int32_t* argmax, SeqRow* rows, int32_t* tokens, int B, BatchStops stops, int32_t* out,
+                           hipStream_t s) {
+  if (B < 1 || B > 64) throw std::runtime_error("batch_feedback: 1 <= B <= 64");
+  hipLaunchKernelGGL(batch_feedback_kernel, dim3(1), dim3(64), 0, s, argmax, rows, tokens, B, stops, out);
   LLMI_HIP(hipGetLastError());
 }
 

@@ -1000,11 +1000,42 @@ bool Session::prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16)
   // at 256-token chunks, 17.4 ms at 512)
   int chunk = 512;
   if (const char* c = getenv("LLMI_PREFILL_CHUNK")) chunk = std::max(1, atoi(c));
+  ensure_prefill_buffers(std::min(chunk, n));
+  const bool f16_all = allow_f16 && prefill_f16_ok();
+  // (A/B: the last layer over every token; scoring needs every token's final row: the same arithmetic)
+  const bool trim = !score_mode_ && getenv("LLMI_PREFILL_FULL_LAST") == nullptr;
+  for (int c0 = 0; c0 < n; c0 += pf_cap_) {
+    const int T = std::min(pf_cap_, n - c0), p0 = pos + c0;
+    const bool last_chunk = c0 + T == n;
+    LLMI_HIP(hipMemcpyAsync(pf_tokens_, tokens + c0, (size_t)T * 4, hipMemcpyHostToDevice, s));
+    prefill_layers(pf_tokens_, T, p0, trim, last_chunk, f16_all, nullptr);
+    if (score_mode_) score_chunk(c0, T, s);  // (before the last token's norm below updates its residual row)
+    if (last_chunk) {  // the last token: final residual + output_norm -> logits (decode tail)
+      NormOut o2;
+      o2.xn = xn_;
+      if (embd_.type == T_F16) o2.x16 = act_.x16;
+      launch_residual_norm(pf_out_ + (size_t)(T - 1) * E, L_.back().post_ffw_norm, pf_resid_ + (size_t)(T - 1) * E,
+                           out_norm_, o2, E, hp_.eps, false, s);
+      tap("result_norm", -1, xn_, (size_t)E * 4, s);
+      record_logits(s);
+    }
+  }
+  return f16_all;
+}
+
+// One chunk of the batched prefill through every layer: T token rows (ids d_tokens, on the device), leaving the
+// last layer's down rows in pf_out_ and its residual rows in pf_resid_.  rows null: consecutive positions p0 .. of
+// the session's own cache (prefill_run).  rows non-null: row b is position rows[b].pos of KV slot rows[b].slot
+// (batch_step; p0 = the longest row's position, a bound for the attention's merge launch) -- the q/k and attention
+// launches take their multi-sequence forms, every other launch is row-independent and runs as it is.
+void Session::prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, bool last_chunk, bool f16_all,
+                             const SeqRow* rows) {
+  hipStream_t s = stream_;
+  const int E = hp_.n_embd, F = hp_.n_ff;
   // attention key splits across work-groups: a constant (never a function of the heads per rank), so tensor-
   // parallel ranks merge the same partials in the same order as one device
   pf_attn_ks_ = 4;
   if (const char* c = getenv("LLMI_PREFILL_ATTN_KS")) pf_attn_ks_ = std::min(std::max(1, atoi(c)), PREFILL_ATTN_KS_MAX);
-  ensure_prefill_buffers(std::min(chunk, n));
   const int XS = pf_xs_, X16 = pf_xs_ * 32;
   const int r = tp_rank_;  // tensor parallel: this rank's column slices (0 on one device)
   const float emb_scale = std::sqrt(static_cast<float>(E));  // model.cpp:337-338
@@ -1013,7 +1044,6 @@ bool Session::prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16)
   // to two f16 roundings; or Q8_0 blocks and the int8 GEMM v5 (LLMI_PREFILL_F16=0, Q8_0 weights, tensor-parallel
   // ranks: a token's scale would differ between the ranks' GELU slices); K-quant layers: Q8_K blocks and v5's
   // K-quant form, or (LLMI_PREFILL_F16=1) f16 rows and GEMM v6.  DESIGN.md section 4.2
-  const bool f16_all = allow_f16 && prefill_f16_ok();
   // the last layer past its K / V appends (one token: the trim below) takes the int8 path: the f16 GEMMs' tiles
   // are slow for T = 1 (4B: gate_up 38 vs 24 us, down 52 vs 43)
   bool f16 = f16_all;
@@ -1041,145 +1071,135 @@ bool Session::prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16)
     if (f16) gather_cols(pf_x16_ + (size_t)t0 * X16, (size_t)X16 * 2, (size_t)cols * 2, T_cur_, s);
     else gather_cols(pf_xq_ + (size_t)t0 * XS, (size_t)XS * sizeof(XBlock), (size_t)(cols / 32) * sizeof(XBlock), T_cur_, s);
   };
-  // (A/B: the last layer over every token; scoring needs every token's final row: the same arithmetic)
-  const bool trim = !score_mode_ && getenv("LLMI_PREFILL_FULL_LAST") == nullptr;
-  for (int c0 = 0; c0 < n; c0 += pf_cap_) {
-    const int T = std::min(pf_cap_, n - c0), p0 = pos + c0;
+  T_cur_ = T;
+  PrefillNorm en;
+  en.table = embd_raw_;
+  en.emb_type = embd_.type;
+  en.row_bytes = embd_row_bytes_;
+  en.tokens = d_tokens;
+  en.emb_scale = emb_scale;
+  en.resid = pf_resid_;
+  en.w_next = L_[0].attn_norm;
+  en.xq = pf_xq_;
+  en.xstride = XS;
+  en.n = E;
+  en.eps = hp_.eps;
+  en.x16 = f16 ? pf_x16_ : nullptr;
+  en.x16stride = X16;
+  en.tscale = f16 ? pf_tscale_ : nullptr;
+  en.q8k = q8k;
+  launch_prefill_norm(en, T, s);
+  for (int l = 0; l < hp_.n_layer; l++) {
+    const LayerDev& Ld = L_[l];
+    const int hd = Ld.hd;
+    t0 = 0;
     T_cur_ = T;
-    const bool last_chunk = c0 + T == n;
-    LLMI_HIP(hipMemcpyAsync(pf_tokens_, tokens + c0, (size_t)T * 4, hipMemcpyHostToDevice, s));
-    PrefillNorm en;
-    en.table = embd_raw_;
-    en.emb_type = embd_.type;
-    en.row_bytes = embd_row_bytes_;
-    en.tokens = pf_tokens_;
-    en.emb_scale = emb_scale;
-    en.resid = pf_resid_;
-    en.w_next = L_[0].attn_norm;
-    en.xq = pf_xq_;
-    en.xstride = XS;
-    en.n = E;
-    en.eps = hp_.eps;
-    en.x16 = f16 ? pf_x16_ : nullptr;
-    en.x16stride = X16;
-    en.tscale = f16 ? pf_tscale_ : nullptr;
-    en.q8k = q8k;
-    launch_prefill_norm(en, T, s);
-    for (int l = 0; l < hp_.n_layer; l++) {
-      const LayerDev& Ld = L_[l];
-      const int hd = Ld.hd;
-      t0 = 0;
-      T_cur_ = T;
-      f16 = f16_all;
-      q8k = pf_kq_ && !f16 ? 1 : 0;
-      xtap("pf_x_qkv", "pf_xs_qkv", l);
-      for (size_t pi = 0, r0 = 0; pi < Ld.qkv.size(); r0 += Ld.qkv[pi].w.rows, pi++)  // q|k|v, or q|k and v (kq)
-        gemm(Ld.qkv[pi].w, pf_out_ + r0, Ld.qkv_rows, true);
-      tap("pf_qkv", l, pf_out_, (size_t)T * Ld.qkv_rows * 4, s);
-      PrefillQK qk;
-      qk.qkv = pf_out_;
-      qk.qkv_stride = Ld.qkv_rows;
-      qk.k_off = Ld.k_off;
-      qk.v_off = Ld.v_off;
-      qk.n_head = nh_;
-      qk.n_head_kv = nkv_;
-      qk.head_dim = hd;
-      qk.q_norm_w = Ld.q_norm;
-      qk.k_norm_w = Ld.k_norm;
-      qk.rope_cs = Ld.is_swa ? rope_swa_ : rope_glb_;
-      qk.attn_scale = hp_.attn_scale;
-      qk.eps = hp_.eps;
-      qk.q_out = pf_q_;
-      qk.k_cache = Ld.kc;
-      qk.v_cache = Ld.vc;
-      qk.max_ctx = max_ctx_;
-      qk.pos0 = p0;
-      launch_prefill_qk(qk, T, s);
-      if (trim && l + 1 == hp_.n_layer) {  // the last layer past its K / V appends: the final token only
-        if (!last_chunk) break;
-        t0 = T - 1;
-        T_cur_ = 1;
-      }
-      // the last layer's attention output and FFN on the int8 path (Q4_0 layers: v5 takes every shape the f16
-      // path does), trimmed or not (LLMI_PREFILL_FULL_LAST: the same arithmetic for the final token)
-      if (l + 1 == hp_.n_layer && !pf_kq_) f16 = false;
-      const int Tq = T_cur_;
-      PrefillAttn at;
-      at.softcap = hp_.attn_softcap;
-      at.q = pf_q_ + (size_t)t0 * nh_ * hd;
-      at.k_cache = Ld.kc;
-      at.v_cache = Ld.vc;
-      at.n_head = nh_;
-      at.n_head_kv = nkv_;
-      at.head_dim = hd;
-      at.max_ctx = max_ctx_;
-      at.pos0 = p0 + t0;
-      const int hb = nh_ * hd / 32;  // this rank's heads' Q8_0 blocks per token
-      const int hr = tp_rep_attn_ ? 0 : r;  // replicated attention: every rank has all heads
-      at.xq = pf_xq_ + (size_t)t0 * XS + (size_t)hr * hb;
-      at.xstride = XS;
-      at.x16 = f16 ? pf_x16_ + (size_t)t0 * X16 + (size_t)hr * nh_ * hd : nullptr;
-      at.x16stride = X16;
-      at.q8k = q8k;
-      at.ks = pf_attn_ks_;
-      at.part = pf_apart_;
-      launch_prefill_attn(at, Tq, s);
-      if (!tp_rep_attn_) xgather(nh_ * hd);
-      tap("pf_q", l, pf_q_, (size_t)T * nh_ * hd * 2, s);
-      tap("kc", l, Ld.kc, (size_t)nkv_ * max_ctx_ * hd * 2, s);
-      tap("vc", l, Ld.vc, (size_t)nkv_ * max_ctx_ * hd * 2, s);
-      xtap("pf_x_o", nullptr, l);
-      gemm(Ld.o.w, pf_out_ + (size_t)r * e_sh_, E, false);
-      if (tp_) gather_cols(pf_out_ + (size_t)t0 * E, (size_t)E * 4, (size_t)e_sh_ * 4, Tq, s);
-      tap("pf_o", l, pf_out_ + (size_t)t0 * E, (size_t)Tq * E * 4, s);
-      PrefillNorm rn;  // post-attention norm + residual, then ffn_norm
-      rn.y = pf_out_ + (size_t)t0 * E;
-      rn.w_post = Ld.post_attn_norm;
-      rn.resid = pf_resid_ + (size_t)t0 * E;
-      rn.w_next = Ld.ffn_norm;
-      rn.xq = pf_xq_ + (size_t)t0 * XS;
-      rn.xstride = XS;
-      rn.n = E;
-      rn.eps = hp_.eps;
-      rn.x16 = f16 ? pf_x16_ + (size_t)t0 * X16 : nullptr;
-      rn.x16stride = X16;
-      rn.tscale = f16 ? pf_tscale_ + t0 : nullptr;
-      rn.q8k = q8k;
-      launch_prefill_norm(rn, Tq, s);
-      tap("pf_resid_attn", l, rn.resid, (size_t)Tq * E * 4, s);
-      xtap("pf_x_gate_up", "pf_xs_gate_up", l);
-      const int FL = tp_ ? f_sh_ : F;  // this rank's hidden units
-      gemm(Ld.gate_up[0].w, pf_out_, 2 * FL, true);
-      tap("pf_gate_up", l, pf_out_ + (size_t)t0 * 2 * FL, (size_t)Tq * 2 * F * 4, s);
-      launch_prefill_gelu(pf_out_ + (size_t)t0 * 2 * FL, FL, layer_gemv_gelu_group(Ld.gate_up[0].w.cols, Ld.gate_up[0].w.type),
-                          pf_xq_ + (size_t)t0 * XS + (size_t)r * (FL / 32), XS, Tq, s,
-                          f16 ? pf_x16_ + (size_t)t0 * X16 + (size_t)r * FL : nullptr, X16, q8k,
-                          f16 ? pf_tscale_ + t0 : nullptr);
-      xgather(FL);
-      xtap("pf_x_down", "pf_xs_down", l);
-      gemm(Ld.down.w, pf_out_ + (size_t)r * e_sh_, E, true);
-      if (tp_) gather_cols(pf_out_ + (size_t)t0 * E, (size_t)E * 4, (size_t)e_sh_ * 4, Tq, s);
-      tap("pf_down", l, pf_out_ + (size_t)t0 * E, (size_t)Tq * E * 4, s);
-      if (l + 1 < hp_.n_layer) {  // post-ffw norm + residual, then the next attn_norm
-        PrefillNorm fn = rn;
-        fn.w_post = Ld.post_ffw_norm;
-        fn.w_next = L_[l + 1].attn_norm;
-        launch_prefill_norm(fn, T, s);
-        tap("pf_resid_ffn", l, pf_resid_, (size_t)T * E * 4, s);
-      }
+    f16 = f16_all;
+    q8k = pf_kq_ && !f16 ? 1 : 0;
+    xtap("pf_x_qkv", "pf_xs_qkv", l);
+    for (size_t pi = 0, r0 = 0; pi < Ld.qkv.size(); r0 += Ld.qkv[pi].w.rows, pi++)  // q|k|v, or q|k and v (kq)
+      gemm(Ld.qkv[pi].w, pf_out_ + r0, Ld.qkv_rows, true);
+    tap("pf_qkv", l, pf_out_, (size_t)T * Ld.qkv_rows * 4, s);
+    PrefillQK qk;
+    qk.qkv = pf_out_;
+    qk.qkv_stride = Ld.qkv_rows;
+    qk.k_off = Ld.k_off;
+    qk.v_off = Ld.v_off;
+    qk.n_head = nh_;
+    qk.n_head_kv = nkv_;
+    qk.head_dim = hd;
+    qk.q_norm_w = Ld.q_norm;
+    qk.k_norm_w = Ld.k_norm;
+    qk.rope_cs = Ld.is_swa ? rope_swa_ : rope_glb_;
+    qk.attn_scale = hp_.attn_scale;
+    qk.eps = hp_.eps;
+    qk.q_out = pf_q_;
+    qk.k_cache = Ld.kc;
+    qk.v_cache = Ld.vc;
+    qk.max_ctx = max_ctx_;
+    qk.pos0 = p0;
+    qk.rows = rows;
+    qk.kv_tab = rows ? bt_kvtab_ + (size_t)l * 2 * LLMI_SEQ_MAX : nullptr;
+    launch_prefill_qk(qk, T, s);
+    if (trim && l + 1 == hp_.n_layer) {  // the last layer past its K / V appends: the final token only
+      if (!last_chunk) return;
+      t0 = T - 1;
+      T_cur_ = 1;
     }
-    if (score_mode_) score_chunk(c0, T, s);  // (before the last token's norm below updates its residual row)
-    if (last_chunk) {  // the last token: final residual + output_norm -> logits (decode tail)
-      NormOut o2;
-      o2.xn = xn_;
-      if (embd_.type == T_F16) o2.x16 = act_.x16;
-      launch_residual_norm(pf_out_ + (size_t)(T - 1) * E, L_.back().post_ffw_norm, pf_resid_ + (size_t)(T - 1) * E,
-                           out_norm_, o2, E, hp_.eps, false, s);
-      tap("result_norm", -1, xn_, (size_t)E * 4, s);
-      record_logits(s);
+    // the last layer's attention output and FFN on the int8 path (Q4_0 layers: v5 takes every shape the f16
+    // path does), trimmed or not (LLMI_PREFILL_FULL_LAST: the same arithmetic for the final token)
+    if (l + 1 == hp_.n_layer && !pf_kq_) f16 = false;
+    const int Tq = T_cur_;
+    PrefillAttn at;
+    at.softcap = hp_.attn_softcap;
+    at.q = pf_q_ + (size_t)t0 * nh_ * hd;
+    at.k_cache = Ld.kc;
+    at.v_cache = Ld.vc;
+    at.n_head = nh_;
+    at.n_head_kv = nkv_;
+    at.head_dim = hd;
+    at.max_ctx = max_ctx_;
+    at.pos0 = p0 + t0;
+    const int hb = nh_ * hd / 32;  // this rank's heads' Q8_0 blocks per token
+    const int hr = tp_rep_attn_ ? 0 : r;  // replicated attention: every rank has all heads
+    at.xq = pf_xq_ + (size_t)t0 * XS + (size_t)hr * hb;
+    at.xstride = XS;
+    at.x16 = f16 ? pf_x16_ + (size_t)t0 * X16 + (size_t)hr * nh_ * hd : nullptr;
+    at.x16stride = X16;
+    at.q8k = q8k;
+    at.ks = pf_attn_ks_;
+    at.part = rows ? bt_apart_ : pf_apart_;
+    at.rows = rows;
+    at.kv_tab = qk.kv_tab;
+    launch_prefill_attn(at, Tq, s);
+    if (rows) {  // time_kernel(10)
+      if ((int)bt_last_attn_.size() != hp_.n_layer) bt_last_attn_.resize((size_t)hp_.n_layer);
+      bt_last_attn_[(size_t)l] = at;
+    }
+    if (!tp_rep_attn_) xgather(nh_ * hd);
+    tap("pf_q", l, pf_q_, (size_t)T * nh_ * hd * 2, s);
+    tap("kc", l, Ld.kc, (size_t)nkv_ * max_ctx_ * hd * 2, s);
+    tap("vc", l, Ld.vc, (size_t)nkv_ * max_ctx_ * hd * 2, s);
+    xtap("pf_x_o", nullptr, l);
+    gemm(Ld.o.w, pf_out_ + (size_t)r * e_sh_, E, false);
+    if (tp_) gather_cols(pf_out_ + (size_t)t0 * E, (size_t)E * 4, (size_t)e_sh_ * 4, Tq, s);
+    tap("pf_o", l, pf_out_ + (size_t)t0 * E, (size_t)Tq * E * 4, s);
+    PrefillNorm rn;  // post-attention norm + residual, then ffn_norm
+    rn.y = pf_out_ + (size_t)t0 * E;
+    rn.w_post = Ld.post_attn_norm;
+    rn.resid = pf_resid_ + (size_t)t0 * E;
+    rn.w_next = Ld.ffn_norm;
+    rn.xq = pf_xq_ + (size_t)t0 * XS;
+    rn.xstride = XS;
+    rn.n = E;
+    rn.eps = hp_.eps;
+    rn.x16 = f16 ? pf_x16_ + (size_t)t0 * X16 : nullptr;
+    rn.x16stride = X16;
+    rn.tscale = f16 ? pf_tscale_ + t0 : nullptr;
+    rn.q8k = q8k;
+    launch_prefill_norm(rn, Tq, s);
+    tap("pf_resid_attn", l, rn.resid, (size_t)Tq * E * 4, s);
+    xtap("pf_x_gate_up", "pf_xs_gate_up", l);
+    const int FL = tp_ ? f_sh_ : F;  // this rank's hidden units
+    gemm(Ld.gate_up[0].w, pf_out_, 2 * FL, true);
+    tap("pf_gate_up", l, pf_out_ + (size_t)t0 * 2 * FL, (size_t)Tq * 2 * F * 4, s);
+    launch_prefill_gelu(pf_out_ + (size_t)t0 * 2 * FL, FL, layer_gemv_gelu_group(Ld.gate_up[0].w.cols, Ld.gate_up[0].w.type),
+                        pf_xq_ + (size_t)t0 * XS + (size_t)r * (FL / 32), XS, Tq, s,
+                        f16 ? pf_x16_ + (size_t)t0 * X16 + (size_t)r * FL : nullptr, X16, q8k,
+                        f16 ? pf_tscale_ + t0 : nullptr);
+    xgather(FL);
+    xtap("pf_x_down", "pf_xs_down", l);
+    gemm(Ld.down.w, pf_out_ + (size_t)r * e_sh_, E, true);
+    if (tp_) gather_cols(pf_out_ + (size_t)t0 * E, (size_t)E * 4, (size_t)e_sh_ * 4, Tq, s);
+    tap("pf_down", l, pf_out_ + (size_t)t0 * E, (size_t)Tq * E * 4, s);
+    if (l + 1 < hp_.n_layer) {  // post-ffw norm + residual, then the next attn_norm
+      PrefillNorm fn = rn;
+      fn.w_post = Ld.post_ffw_norm;
+      fn.w_next = L_[l + 1].attn_norm;
+      launch_prefill_norm(fn, T, s);
+      tap("pf_resid_ffn", l, pf_resid_, (size_t)T * E * 4, s);
     }
   }
-  return f16_all;
 }
 
 // Fast path with every projection a gemv_q4_0_layer launch: 5 launches per
@@ -2325,6 +2345,7 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
     LLMI_HIP(hipStreamSynchronize(stream_));
     return;
   }
+  if (which == 10) return time_batch_attn(reps, us, bytes);  // (session_batch.cpp)
   if (which == 9) {  // the fused scorer's two launches over the most recently scored chunk (its rows are still there)
     *us = *bytes = 0.0;
     if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;

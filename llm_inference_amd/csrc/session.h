@@ -83,6 +83,14 @@ class Session {
   // llmi_session_score
   void score(const int32_t* tokens, int n_tokens, int pos, const int32_t* targets, float* logprob, float* lse,
              int32_t* argmax);
+  // several sequences per step (session_batch.cpp)
+  void seq_reserve(int n_seq);
+  int n_seq() const { return n_seq_; }
+  void seq_copy(int dst, int src, int n_pos);
+  void batch_forward(const int32_t* tokens, const int32_t* slots, const int32_t* pos, int B, float* logits,
+                     int32_t* argmax, float* lse);
+  void batch_generate(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
+                      const int32_t* stop, int n_stop, int32_t* out);
   void enqueue(int32_t first, int pos, int n_steps);
   void sync(int32_t* out_tokens, int n);
   void set_sampler(const llmi_sampler* sp);  // null or temperature 0: greedy
@@ -114,6 +122,9 @@ class Session {
   void prefill(const int32_t* tokens, int n, int pos);  // batched (k_prefill.hip)
   bool prefill_f16_ok() const;  // the batched prefill's activations as f16 rows (GEMM v7 / v6)
   bool prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16);  // true: ran the f16 path
+  // one chunk's launches through every layer (prefill_run's consecutive positions, or batch_step's rows)
+  void prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, bool last_chunk, bool f16_all,
+                      const SeqRow* rows);
   void gather_cols(void* buf, size_t pitch_b, size_t slice_b, int T, hipStream_t s);
   void ensure_prefill_buffers(int cap);
   void record_layers(hipStream_t s, bool x_q8);
@@ -301,6 +312,28 @@ class Session {
   float *sc_tl_ = nullptr, *sc_lp_ = nullptr, *sc_lse_ = nullptr;
   std::vector<int32_t> sc_h_tgt_, sc_h_amax_;  // host: the call's resolved targets, its results
   std::vector<float> sc_h_lp_, sc_h_lse_;
+  // several sequences per step: KV slots (slot 0 = L_[l].kc / vc) and the batch step's device-resident rows
+  int n_seq_ = 1;
+  bool seq_reserved_ = false;
+  std::vector<uint16_t*> bt_h_kvtab_;  // host image of bt_kvtab_
+  uint16_t** bt_kvtab_ = nullptr;      // [n_layer][LLMI_SEQ_MAX][2]: slot's K, V cache of the layer (null: unreserved)
+  SeqRow *bt_rows_ = nullptr, *bt_trows_ = nullptr;  // [LLMI_SEQ_MAX]: the step's rows; time_kernel(10)'s copy
+  int32_t* bt_tok_ = nullptr;          // [LLMI_SEQ_MAX] the step's token ids
+  uint16_t* bt_row0_ = nullptr;        // [LLMI_SEQ_MAX][n_embd] f16: position-0 rows' final-norm rows (batch_row0)
+  float* bt_r0_lse_ = nullptr;         // ... and their (lse | scratch log-prob) and arg-max, from the f64 row reduce
+  int32_t* bt_r0_amax_ = nullptr;
+  float* bt_apart_ = nullptr;          // attention partials [head][row][PREFILL_ATTN_KS_MAX]
+  int32_t* bt_ring_ = nullptr;         // the greedy loop's ids [n_steps][B]
+  size_t bt_ring_cap_ = 0;
+  std::vector<PrefillAttn> bt_last_attn_;  // the most recent batch step's attention launches, per layer
+  std::vector<SeqRow> bt_last_rows_;       // ... and its rows (host)
+  void batch_check(const char* fn, const int32_t* tokens, const int32_t* slots, const int32_t* pos, int B,
+                   int n_steps) const;
+  void batch_row0(int32_t token, int slot, int b);  // row b of the step being set up
+  // the step's launches for B rows already in bt_tok_ / bt_rows_ (max_pos: the longest row's position; row0: the
+  // rows at position 0, whose scorer rows come from bt_row0_); returns whether the f16 path ran
+  bool batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0);
+  void time_batch_attn(int reps, double* us, double* bytes);
 };
 
 }  // namespace llmi

@@ -162,6 +162,11 @@ struct PrefillGemm16 {  // f16 activations [T][xstride elements] (k_prefill.hip 
   int ostride = 0;
   const float* tscale = nullptr;  // [T] 2^s of the x16 rows (null: 1)
 };
+// A row of a multi-sequence launch (Session::batch_*): the token at position `pos` of KV slot
+// `slot`.  pos < 0: a row of the greedy loop that has emitted a stop id -- it appends nothing and attends nothing.
+struct SeqRow {
+  int slot, pos;
+};
 struct PrefillQK {
   const float* qkv = nullptr;  // [T][qkv_stride]
   int qkv_stride = 0, k_off = 0, v_off = 0, n_head = 0, n_head_kv = 0, head_dim = 0;
@@ -171,6 +176,11 @@ struct PrefillQK {
   uint16_t* q_out = nullptr;  // [T][n_head][head_dim] f16, scaled
   uint16_t *k_cache = nullptr, *v_cache = nullptr;
   int max_ctx = 0, pos0 = 0;
+  // multi-sequence form (rows non-null): token row b takes rope row rows[b].pos and appends to slot rows[b].slot,
+  // whose caches are kv_tab[2 slot] (K) and kv_tab[2 slot + 1] (V) -- this layer's entries of the session's slot
+  // table; k_cache / v_cache / pos0 are not read
+  const SeqRow* rows = nullptr;
+  uint16_t* const* kv_tab = nullptr;
 };
 struct PrefillAttn {
   const uint16_t* q = nullptr;
@@ -186,7 +196,21 @@ struct PrefillAttn {
   int ks = 1;
   float* part = nullptr;
   float softcap = 0.0f;     // attention.logit_softcapping (model.cpp:511-513); 0: none
+  // multi-sequence decode form (rows non-null; launch_prefill_attn's T = the rows): row b is one query at position
+  // rows[b].pos over keys 0 .. rows[b].pos of its slot's caches (kv_tab as in PrefillQK), computed exactly as the
+  // single-sequence launch computes Tq = 1 at pos0 = rows[b].pos: the row takes the place of the query block, so
+  // q, the outputs and the partials are indexed by b.  part: [head][row][ks] partials
+  const SeqRow* rows = nullptr;
+  uint16_t* const* kv_tab = nullptr;
 };
+// the greedy batch loop's feedback (after the scorer's merge): a live row b takes id = argmax[b] -> out[b]; a stop id
+// ends the row (rows[b].pos = -1), any other id becomes tokens[b] at rows[b].pos + 1.  Ended rows: out[b] = -1
+struct BatchStops {
+  int32_t id[4];
+  int n;
+};
+void launch_batch_feedback(const int32_t* argmax, SeqRow* rows, int32_t* tokens, int B, BatchStops stops, int32_t* out,
+                           hipStream_t s);
 constexpr int PREFILL_ATTN_KS_MAX = 8;
 void launch_prefill_norm(const PrefillNorm& a, int T, hipStream_t s);
 bool prefill_gemm_supported(const DevWeight& w);

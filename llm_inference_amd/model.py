@@ -5,10 +5,13 @@ device session of include/llmi.h.
     logits = m.forward([tok, ...], pos)   # Model::forward     model.cpp:706-1049
     ids = m.generate(first, pos, n)       # main.cpp:172-224 greedy loop, on device
     m.set_sampler(temperature=1.0, top_k=64, top_p=0.95, seed=1)   # ... or seeded sampling in the same loop
+    m.reserve_sequences(8)                # KV slots: several sequences per step
+    ids = m.batch_generate(firsts, slots, positions, n)   # int32 [n, B], greedy, on device
 """
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
@@ -45,6 +48,14 @@ class TPGroup:
 
     def __del__(self):
         self.close()
+
+
+@dataclass
+class BatchResult:
+    """Model.batch_forward: per row the greedy id, the log-sum-exp of its logits and (want_logits) the logits."""
+    argmax: np.ndarray            # int32 [B]
+    lse: np.ndarray               # float32 [B]
+    logits: Optional[np.ndarray]  # float32 [B, vocab] or None
 
 
 class Model:
@@ -159,6 +170,46 @@ class Model:
             check(lib().llmi_session_generate(self.h, first, pos, n_steps, ptr(out)))
         finally:
             self.set_sampler(before)
+        return out[:n_steps]
+
+    def reserve_sequences(self, n: int) -> None:
+        """llmi_session_seq_reserve: KV slots 0..n-1 (slot 0 is the session's own cache, where forward() / score()
+        leave a prompt); may be called again with a larger n."""
+        check(lib().llmi_session_seq_reserve(self.h, n))
+        self.info = self.get_info()
+
+    def copy_sequence(self, dst: int, src: int, n_pos: int) -> None:
+        """llmi_session_seq_copy: K/V rows [0, n_pos) of every layer, slot src -> slot dst (moves or forks a prompt)."""
+        check(lib().llmi_session_seq_copy(self.h, dst, src, n_pos))
+
+    def _batch_rows(self, tokens, slots, pos):
+        t, sl, p = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (tokens, slots, pos))
+        if not (t.size == sl.size == p.size):
+            raise ValueError("tokens, slots and pos must have one entry per row")
+        return t, sl, p
+
+    def batch_forward(self, tokens: Sequence[int], slots: Sequence[int], pos: Sequence[int],
+                      want_logits: bool = False) -> BatchResult:
+        """llmi_session_batch_forward: one step for B rows -- row b runs tokens[b] at position pos[b] of slot
+        slots[b].  Each row's results are, bit for bit, the last position of score() / forward() of the same prompt
+        on a single-sequence session.  want_logits: [B, vocab] logits for host-side
+        sampling (slow: one output-table read per row)."""
+        t, sl, p = self._batch_rows(tokens, slots, pos)
+        am, lse = np.zeros(t.size, np.int32), np.zeros(t.size, np.float32)
+        lg = np.zeros((t.size, self.vocab), np.float32) if want_logits else None
+        check(lib().llmi_session_batch_forward(self.h, ptr(t), ptr(sl), ptr(p), t.size,
+                                               ptr(lg) if lg is not None else None, ptr(am), ptr(lse)))
+        return BatchResult(am, lse, lg)
+
+    def batch_generate(self, first: Sequence[int], slots: Sequence[int], pos: Sequence[int], n_steps: int,
+                       stop: Sequence[int] = ()) -> np.ndarray:
+        """llmi_session_batch_generate: the greedy loop for B rows on the device; returns int32 [n_steps, B].  A row
+        that emits one of `stop` (at most 4 ids) keeps that id, then -1, and appends nothing more to its slot."""
+        t, sl, p = self._batch_rows(first, slots, pos)
+        st = np.ascontiguousarray(stop, np.int32).reshape(-1)
+        out = np.zeros((max(n_steps, 1), max(t.size, 1)), np.int32)
+        check(lib().llmi_session_batch_generate(self.h, ptr(t), ptr(sl), ptr(p), t.size, n_steps,
+                                                ptr(st) if st.size else None, st.size, ptr(out)))
         return out[:n_steps]
 
     def enqueue(self, first: int, pos: int, n_steps: int) -> None:
