@@ -193,8 +193,8 @@ int llmi_session_seq_reserve(llmi_session* s, int n_seq);
 int llmi_session_seq_copy(llmi_session* s, int dst, int src, int n_pos);
 /* One step for B rows: row b runs token tokens[b] at position pos[b] of slot slots[b] (appends its K/V there,
  * attends keys 0..pos[b] of that slot).  argmax[b] / lse[b] (may be NULL) come from the fused scorer; logits
- * ([B][vocab], may be NULL) from the F16 logits GEMV row by row (slow: one table read per row; for host-side
- * sampling).  Slots must be distinct within a call.  1 <= B <= n_seq. */
+ * ([B][vocab], may be NULL) from the multi-row F16 logits GEMV (one table read per block of rows, section 13; for
+ * host-side sampling).  Slots must be distinct within a call.  1 <= B <= n_seq. */
 int llmi_session_batch_forward(llmi_session* s, const int32_t* tokens, const int32_t* slots, const int32_t* pos,
                                int B, float* logits, int32_t* argmax, float* lse);
 /* Greedy loop on the device, no host round trip between steps: step i feeds row b's arg-max back as its next token
@@ -268,6 +268,28 @@ int llmi_session_set_sampler(llmi_session* s, const llmi_sampler* sp);
  * (-1 past the last) and their integer weights, *n_cand = K', *n_nucleus = n (each may be NULL). */
 int llmi_sample_logits(const float* logits, size_t n, const llmi_sampler* sp, int pos, int32_t* token,
                        int32_t* cand, uint64_t* cand_q, int* n_cand, int* n_nucleus);
+
+/* Sampling inside the batch loop: llmi_session_batch_generate with a sampler per row
+ * (samplers: B entries; NULL: LLMI_E_ARG).  The loop stays on the device: per step the batch step, the rows' full
+ * logits (the F16 logits GEMV for several rows at once: one table read per block of rows, each row's logits bit for
+ * bit forward's), the final soft-cap and the sampler's two launches for all rows, the second carrying the feedback.
+ * Contract: a row that runs x[p] at position p of its slot (under the row contract above on the slot's K/V) emits
+ * exactly the rule of llmi_session_set_sampler applied to the logits of llmi_session_forward(x[0..p], 0) on a fresh
+ * single-sequence session, with pos = p and its sampler's seed -- whatever B, the other rows and their samplers,
+ * the slot, the row order and the chunking of n_steps.  A row whose sampler has temperature == 0 is greedy: its ids
+ * are llmi_session_batch_generate's.  Checks, refusals, stop ids and `out` as llmi_session_batch_generate; each
+ * sampler is validated as llmi_session_set_sampler validates one (LLMI_E_ARG, the message names the field and the
+ * row).  The session's own sampler is neither read nor changed. */
+int llmi_session_batch_generate_sampled(llmi_session* s, const int32_t* first, const int32_t* slots, const int32_t* pos,
+                                        int B, int n_steps, const int32_t* stop, int n_stop,
+                                        const llmi_sampler* samplers, int32_t* out);
+
+/* op level, host pointers, synchronous: the multi-row F16 logits GEMV alone.  x16: [T][E] f16 bits, w16: [V][E] f16
+ * bits (row-major), logits: [T][V], softcap <= 0: none.  logits[t] carries the bits of the fast F16
+ * llmi_mat_vec_mul of w16 with row t.  E % 128 == 0 and E <= 6144, else LLMI_E_SIZE.  llmi_logits_rows_rb: the rows
+ * that share one read of the table at width E (0: E is not supported). */
+int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits);
+int llmi_logits_rows_rb(int E);
 
 /* Enqueue n_steps decode steps without waiting (bench); llmi_session_sync
  * waits and copies the produced tokens (may be NULL). */
@@ -346,7 +368,11 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *       plus the chunk's [T][E] f16 rows (0 / 0 when nothing was scored yet or the row path is in use);
  *  10 = the multi-sequence attention launch (+ its merge) of the most recent batch step, one pass over the layers;
  *       bytes = the K and V rows 0..pos[b] of every row that was live in that step, per layer (0 / 0 before any
- *       batch step).
+ *       batch step);
+ *  11 = the sampled batch loop's token selection over the most recent sampled batch step's rows: the multi-row
+ *       logits GEMV, the sampler's select and finalize launches (no feedback); bytes = table reads
+ *       (ceil(B / llmi_logits_rows_rb(n_embd))) x the F16 table plus the B x vocab f32 logits (0 / 0 before any
+ *       sampled batch step).
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

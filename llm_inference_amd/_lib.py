@@ -106,6 +106,10 @@ _SIGS = {
     "llmi_session_seq_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "llmi_session_batch_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "llmi_session_batch_generate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "llmi_session_batch_generate_sampled": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
+                                                      C.POINTER(Sampler), _vp]),
+    "llmi_logits_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp]),
+    "llmi_logits_rows_rb": (C.c_int, [C.c_int]),
     "llmi_score_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),
     "llmi_session_generate": (C.c_int, [_vp, _i32, C.c_int, C.c_int, _vp]),
     "llmi_session_dump": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_char_p]),

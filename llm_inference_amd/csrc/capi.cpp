@@ -471,6 +471,45 @@ int llmi_session_batch_generate(llmi_session* s, const int32_t* first, const int
   });
 }
 
+int llmi_session_batch_generate_sampled(llmi_session* s, const int32_t* first, const int32_t* slots, const int32_t* pos,
+                                        int B, int n_steps, const int32_t* stop, int n_stop,
+                                        const llmi_sampler* samplers, int32_t* out) {
+  return guard([&] {
+    if (!s || !first || !slots || !pos || (!out && n_steps > 0))
+      throw status_error(LLMI_E_ARG, "batch_generate_sampled: null pointer");
+    s->s->batch_generate_sampled(first, slots, pos, B, n_steps, stop, n_stop, samplers, out);
+  });
+}
+
+int llmi_logits_rows_rb(int E) { return logits_rows_rb(E); }
+
+int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits) {
+  return guard([&] {
+    if (!x16 || !w16 || !logits) throw status_error(LLMI_E_ARG, "logits_rows: null pointer");
+    if (T <= 0 || V <= 0) throw status_error(LLMI_E_ARG, "logits_rows: T and V must be positive");
+    if (logits_rows_rb(E) == 0)
+      throw status_error(LLMI_E_SIZE, "logits_rows: E must be a multiple of 128, at most 6144");
+    if ((long long)T * V > (long long)INT32_MAX) throw status_error(LLMI_E_SIZE, "logits_rows: T x V too large");
+    Ctx& c = ctx();
+    const size_t xb = (size_t)T * E * 2, wb = (size_t)V * E * 2, ob = (size_t)T * V * 4;
+    uint16_t* xd = (uint16_t*)c.get(0, xb);
+    uint16_t* wd = (uint16_t*)c.get(1, wb);
+    float* od = (float*)c.get(2, ob);
+    LLMI_HIP(hipMemcpyAsync(xd, x16, xb, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(wd, w16, wb, hipMemcpyHostToDevice, c.stream));
+    DevWeight w;
+    w.type = T_F16;
+    w.rows = V;
+    w.cols = E;
+    w.qs = wd;
+    w.bytes = wb;
+    launch_gemv_f16_rows(w, xd, E, T, od, c.stream);
+    if (softcap > 0.0f) launch_softcap(od, T * V, softcap, c.stream);
+    LLMI_HIP(hipMemcpyAsync(logits, od, ob, hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipStreamSynchronize(c.stream));
+  });
+}
+
 int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
                     const int32_t* targets, float* logprob, float* lse, int32_t* argmax) {
   return guard([&] {

@@ -2,6 +2,7 @@
 // selection over a logits row and the one-work-group finalize with the token feedback.  The decode loop's folded
 // form of the finalize (with the next step's embed_norm) is in k_session.hip.
 #include "sample.h"
+#include "session_kernels.h"
 
 namespace llmi {
 
@@ -19,12 +20,11 @@ void launch_set_sampler(SamplerDev* d, float temperature, int top_k, float top_p
   LLMI_HIP(hipGetLastError());
 }
 
-// work-group b: logits [b EPT 1024, (b + 1) EPT 1024) -> its top K keys in surv[b 256 ..], the other slots 0
+// work-group g: logits [g EPT 1024, (g + 1) EPT 1024) -> its top K keys in surv[g 256 ..], the other slots 0
 template <int EPT>
-__global__ __launch_bounds__(SAMPLE_THREADS) void sample_select_kernel(const float* __restrict__ logits, int V,
-                                                                       const SamplerDev* __restrict__ sp,
-                                                                       unsigned long long* __restrict__ surv) {
-  __shared__ SampleShared sh;
+__device__ __forceinline__ void sample_select_block(const float* __restrict__ logits, int V,
+                                                    const SamplerDev* __restrict__ sp,
+                                                    unsigned long long* __restrict__ surv, SampleShared& sh) {
   const int t = threadIdx.x;
   int K = sp->top_k;
   if (K <= 0 || K > SAMPLE_MAX_K) K = SAMPLE_MAX_K;
@@ -47,6 +47,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_select_kernel(const flo
     }
   __syncthreads();
   if (t < SAMPLE_MAX_K) surv[(size_t)blockIdx.x * SAMPLE_MAX_K + t] = sh.key[t];
+}
+
+template <int EPT>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_select_kernel(const float* __restrict__ logits, int V,
+                                                                       const SamplerDev* __restrict__ sp,
+                                                                       unsigned long long* __restrict__ surv) {
+  __shared__ SampleShared sh;
+  sample_select_block<EPT>(logits, V, sp, surv, sh);
 }
 
 void launch_sample_select(const float* logits, int V, const SamplerDev* sp, unsigned long long* surv, hipStream_t s) {
@@ -88,6 +96,79 @@ void launch_sample_finalize(const unsigned long long* surv, int V, const Sampler
   if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
   hipLaunchKernelGGL(sample_finalize_kernel, dim3(1), dim3(SAMPLE_THREADS), 0, s, surv, g * SAMPLE_MAX_K, sp, d_pos,
                      d_token, ring, ring_idx, ring_cap, keys, n_keys, dbg);
+  LLMI_HIP(hipGetLastError());
+}
+
+// ---- the batch loop's rows ----
+// Work-group (g, b): sample_select_kernel's work-group g on logits row b with sp[b], into surv[b][g].  A row that
+// has ended (pos < 0) or decodes greedily (temperature 0: its id is the scorer's arg-max) selects nothing.
+template <int EPT>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_select_rows_kernel(const float* __restrict__ logits, int V,
+                                                                            const SamplerDev* __restrict__ sp,
+                                                                            const SeqRow* __restrict__ rows,
+                                                                            unsigned long long* __restrict__ surv) {
+  __shared__ SampleShared sh;
+  const int b = blockIdx.y;
+  if (rows[b].pos < 0 || sp[b].temperature == 0.0f) return;
+  sample_select_block<EPT>(logits + (size_t)b * V, V, sp + b, surv + (size_t)b * SAMPLE_MAX_GROUPS * SAMPLE_MAX_K, sh);
+}
+
+void launch_sample_select_rows(const float* logits, int V, int B, const SamplerDev* sp, const SeqRow* rows,
+                               unsigned long long* surv, hipStream_t s) {
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  if (B < 1 || B > 64) throw std::runtime_error("sample_select_rows: 1 <= B <= 64");
+  const dim3 grid(g, B);
+  if (ept == 4)
+    hipLaunchKernelGGL(sample_select_rows_kernel<4>, grid, dim3(SAMPLE_THREADS), 0, s, logits, V, sp, rows, surv);
+  else if (ept == 8)
+    hipLaunchKernelGGL(sample_select_rows_kernel<8>, grid, dim3(SAMPLE_THREADS), 0, s, logits, V, sp, rows, surv);
+  else
+    hipLaunchKernelGGL(sample_select_rows_kernel<16>, grid, dim3(SAMPLE_THREADS), 0, s, logits, V, sp, rows, surv);
+  LLMI_HIP(hipGetLastError());
+}
+
+// Work-group b: row b's id -- sample_finalize_block on its survivors with sp[b] at pos = rows[b].pos, or argmax[b]
+// for a greedy row -- then batch_feedback_kernel's feedback for the row (feedback 0: time_kernel, nothing written).
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_finalize_rows_kernel(
+    const unsigned long long* __restrict__ surv, int n_surv, const SamplerDev* __restrict__ sp,
+    const int32_t* __restrict__ argmax, SeqRow* __restrict__ rows, int32_t* __restrict__ tokens, BatchStops stops,
+    int32_t* __restrict__ out, int feedback) {
+  __shared__ SampleShared sh;
+  const int b = blockIdx.x;
+  const SeqRow sr = rows[b];
+  __syncthreads();  // (thread 0 rewrites rows[b] below)
+  if (sr.pos < 0) {
+    if (threadIdx.x == 0 && feedback) out[b] = -1;
+    return;
+  }
+  int id;
+  if (sp[b].temperature == 0.0f)
+    id = argmax[b];
+  else
+    id = sample_finalize_block(surv + (size_t)b * SAMPLE_MAX_GROUPS * SAMPLE_MAX_K, n_surv, sp + b, sr.pos, nullptr, sh);
+  if (threadIdx.x != 0 || !feedback) return;
+  out[b] = id;
+  bool stop = false;
+  for (int i = 0; i < 4; i++) stop = stop || (i < stops.n && stops.id[i] == id);
+  if (stop) {
+    rows[b].pos = -1;
+  } else {
+    tokens[b] = id;
+    rows[b].pos = sr.pos + 1;
+  }
+}
+
+void launch_sample_finalize_rows(const unsigned long long* surv, int V, int B, const SamplerDev* sp,
+                                 const int32_t* argmax, SeqRow* rows, int32_t* tokens, const BatchStops& stops,
+                                 int32_t* out, bool feedback, hipStream_t s) {
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  if (B < 1 || B > 64) throw std::runtime_error("sample_finalize_rows: 1 <= B <= 64");
+  hipLaunchKernelGGL(sample_finalize_rows_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, surv, g * SAMPLE_MAX_K, sp,
+                     argmax, rows, tokens, stops, out, feedback ? 1 : 0);
   LLMI_HIP(hipGetLastError());
 }
 

@@ -62,6 +62,16 @@ void launch_round_f16(const float* x, int n, uint16_t* out, hipStream_t s);
 void launch_gemv(const DevWeight& w, const ActBuf& x, float* o, GemvMode mode, hipStream_t s,
                  unsigned long long* amax_key = nullptr);
 
+// The fast F16 GEMV for R activation rows at once: x16 [R][xstride] f16 rows (xstride % 8
+// == 0), out [R][w.rows] f32; out[r] carries the bits launch_gemv(GEMV_FAST) writes for row r alone.  The widths of
+// launch_gemv's pipelined row kernel only (cols % 128 == 0, cols <= 6144).  The table is read once per block of
+// logits_rows_rb(cols) activation rows, which wait in LDS: 8 rows up to 3840 columns (60 KB), 4 above (at most
+// 48 KB); 0: the width is not supported.
+constexpr int logits_rows_rb(int cols) {
+  return (cols <= 0 || cols % 128 != 0 || cols > 6144) ? 0 : cols <= 3840 ? 8 : 4;
+}
+void launch_gemv_f16_rows(const DevWeight& w, const uint16_t* x16, int xstride, int R, float* out, hipStream_t s);
+
 // elementwise / norms
 // o = rms_norm(x) [* w if w]  per row of n, n_rows rows; exact = serial FMA sum
 void launch_rms_norm(const float* x, const float* w, float* o, int n, int n_rows, double eps, bool exact,

@@ -310,6 +310,20 @@ void launch_sample_finalize(const unsigned long long* surv, int V, const Sampler
                             int32_t* d_token, int32_t* ring, int32_t* ring_idx, int ring_cap,
                             unsigned long long* keys, int n_keys, SampleDbg* dbg, hipStream_t s);
 
+// The batch loop's rows (Session::batch_generate_sampled): the two launches over B logits rows
+// [B][V], sampler sp[b] per row, survivors surv [B][SAMPLE_MAX_GROUPS x 256].  Row b is the one-row launches' work
+// on logits row b with sp[b] at pos = rows[b].pos; a row with sp[b].temperature == 0 is greedy (its id is
+// argmax[b], the fused scorer's) and a row with rows[b].pos < 0 has ended: both leave the select launch at once.
+// The finalize launch is also the row's launch_batch_feedback (session_kernels.h): out[b] = id (-1: ended), a stop
+// id ends the row, any other id becomes tokens[b] at rows[b].pos + 1.  feedback false (time_kernel): writes nothing.
+struct SeqRow;
+struct BatchStops;
+void launch_sample_select_rows(const float* logits, int V, int B, const SamplerDev* sp, const SeqRow* rows,
+                               unsigned long long* surv, hipStream_t s);
+void launch_sample_finalize_rows(const unsigned long long* surv, int V, int B, const SamplerDev* sp,
+                                 const int32_t* argmax, SeqRow* rows, int32_t* tokens, const BatchStops& stops,
+                                 int32_t* out, bool feedback, hipStream_t s);
+
 // k_session.hip: launch_sample_finalize with the feedback, then the next step's embed_norm (as
 // launch_finalize_embed_norm)
 struct NormOut;

@@ -91,6 +91,9 @@ class Session {
                      int32_t* argmax, float* lse);
   void batch_generate(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                       const int32_t* stop, int n_stop, int32_t* out);
+  // per-row seeded sampling inside the batch loop; samplers: B entries
+  void batch_generate_sampled(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
+                              const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);
   void enqueue(int32_t first, int pos, int n_steps);
   void sync(int32_t* out_tokens, int n);
   void set_sampler(const llmi_sampler* sp);  // null or temperature 0: greedy
@@ -332,8 +335,23 @@ class Session {
   void batch_row0(int32_t token, int slot, int b);  // row b of the step being set up
   // the step's launches for B rows already in bt_tok_ / bt_rows_ (max_pos: the longest row's position; row0: the
   // rows at position 0, whose scorer rows come from bt_row0_); returns whether the f16 path ran
-  bool batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0);
+  // score false: the fused scorer's launches are left out (a sampled step none of whose rows is greedy)
+  bool batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0, bool score = true);
   void time_batch_attn(int reps, double* us, double* bytes);
+  // the batch loop: greedy (samplers null: batch_generate) or with a sampler per row
+  void batch_loop(const char* fn, const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
+                  const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);
+  // final-norm rows sc_x16_[0..B) -> bt_logits_ [B][vocab], soft-capped: the multi-row logits GEMV, or launch_gemv
+  // row by row for a table width it does not take
+  void batch_logits(int B, hipStream_t s);
+  SamplerDev* bt_samplers_ = nullptr;         // [LLMI_SEQ_MAX] the sampled loop's per-row samplers
+  float* bt_logits_ = nullptr;                // [bt_logits_cap_][vocab] grow-only
+  unsigned long long* bt_surv_ = nullptr;     // [bt_logits_cap_][SAMPLE_MAX_GROUPS x 256]
+  int bt_logits_cap_ = 0, bt_surv_cap_ = 0;
+  int bt_samp_B_ = 0;                         // rows of the most recent sampled batch step (time_kernel(11))
+  std::vector<SeqRow> bt_samp_rows_;          // ... as it ran them
+  void ensure_batch_logits(int B, bool surv);
+  void time_batch_sampling(int reps, double* us, double* bytes);
 };
 
 }  // namespace llmi

@@ -1,6 +1,7 @@
 // session_batch.cpp -- several sequences per step (llmi_session_seq_* / llmi_session_batch_*).
 // A batch step is the batched prefill's launch sequence over B token rows (Session::prefill_layers), each row a
-// position of its own KV slot, then the scorer's rows; the greedy loop adds one feedback launch per step.
+// position of its own KV slot, then the scorer's rows; the greedy loop adds one feedback launch per step, the
+// sampled loop (section 13) the rows' full logits and the sampler's two multi-row launches.
 #include "session.h"
 
 #include <algorithm>
@@ -125,7 +126,7 @@ void Session::batch_row0(int32_t token, int slot, int b) {
   LLMI_HIP(hipMemcpyAsync(dst, act_.x16, (size_t)hp_.n_embd * 2, hipMemcpyDeviceToDevice, stream_));
 }
 
-bool Session::batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0) {
+bool Session::batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0, bool score) {
   hipStream_t s = stream_;
   const int E = hp_.n_embd;
   ensure_prefill_buffers(B);
@@ -142,6 +143,7 @@ bool Session::batch_step(int B, int max_pos, bool allow_f16, const std::vector<i
   launch_residual_norm_rows16(pf_out_, E, L_.back().post_ffw_norm, pf_resid_, E, out_norm_, sc_x16_, E, E, B, hp_.eps, s);
   for (int b : row0)
     LLMI_HIP(hipMemcpyAsync(sc_x16_ + (size_t)b * E, bt_row0_ + (size_t)b * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
+  if (!score) return f16_all;
   ScoreArgs a;
   a.x16 = sc_x16_;
   a.xstride = E;
@@ -199,14 +201,13 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
     LLMI_HIP(hipMemcpyAsync(hx.data(), sc_x16_, hx.size() * 2, hipMemcpyDeviceToHost, s));
     LLMI_HIP(hipMemcpyAsync(am.data(), sc_amax_, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     LLMI_HIP(hipMemcpyAsync(ls.data(), sc_lse_, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    if (logits)  // forward's logits GEMV on each row's f16 final-norm row (one table read per row)
-      for (int i = 0; i < n; i++) {
-        LLMI_HIP(hipMemcpyAsync(act_.x16, sc_x16_ + (size_t)i * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
-        launch_gemv(logits_w_, act_, logits_, GEMV_FAST, s, nullptr);
-        if (hp_.final_softcap > 0.0f) launch_softcap(logits_, v_rows_, hp_.final_softcap, s);
-        LLMI_HIP(hipMemcpyAsync(logits + (size_t)idx[(size_t)i] * vocab_, logits_, (size_t)vocab_ * 4,
-                                hipMemcpyDeviceToHost, s));
-      }
+    if (logits) {  // forward's logits GEMV on the rows' f16 final-norm rows
+      ensure_batch_logits(n, false);
+      batch_logits(n, s);
+      for (int i = 0; i < n; i++)
+        LLMI_HIP(hipMemcpyAsync(logits + (size_t)idx[(size_t)i] * vocab_, bt_logits_ + (size_t)i * vocab_,
+                                (size_t)vocab_ * 4, hipMemcpyDeviceToHost, s));
+    }
     LLMI_HIP(hipStreamSynchronize(s));
     check_device_error();
     for (int i = 0; i < n; i++) {
@@ -233,24 +234,82 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
   }
 }
 
+void Session::ensure_batch_logits(int B, bool surv) {  // grow-only, as the prefill's chunk buffers
+  if (B > bt_logits_cap_) {
+    bt_logits_ = dalloc<float>((size_t)B * vocab_);
+    bt_logits_cap_ = B;
+  }
+  if (surv && B > bt_surv_cap_) {
+    bt_surv_ = dalloc<unsigned long long>((size_t)B * SAMPLE_MAX_GROUPS * SAMPLE_MAX_K);
+    bt_surv_cap_ = B;
+  }
+}
+
+void Session::batch_logits(int B, hipStream_t s) {
+  const int E = hp_.n_embd;
+  if (logits_rows_rb(E) != 0) {
+    launch_gemv_f16_rows(logits_w_, sc_x16_, E, B, bt_logits_, s);
+  } else {  // one table read per row
+    for (int i = 0; i < B; i++) {
+      LLMI_HIP(hipMemcpyAsync(act_.x16, sc_x16_ + (size_t)i * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
+      launch_gemv(logits_w_, act_, bt_logits_ + (size_t)i * vocab_, GEMV_FAST, s, nullptr);
+    }
+  }
+  if (hp_.final_softcap > 0.0f) launch_softcap(bt_logits_, B * vocab_, hp_.final_softcap, s);
+}
+
 void Session::batch_generate(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                              const int32_t* stop, int n_stop, int32_t* out) {
-  batch_check("batch_generate", first, slots, pos, B, n_steps);
-  if (n_stop < 0 || n_stop > 4) throw status_error(LLMI_E_ARG, "batch_generate: at most 4 stop ids (n_stop)");
-  if (n_stop > 0 && !stop) throw status_error(LLMI_E_ARG, "batch_generate: null pointer (stop)");
+  batch_loop("batch_generate", first, slots, pos, B, n_steps, stop, n_stop, nullptr, out);
+}
+
+void Session::batch_generate_sampled(const int32_t* first, const int32_t* slots, const int32_t* pos, int B,
+                                     int n_steps, const int32_t* stop, int n_stop, const llmi_sampler* samplers,
+                                     int32_t* out) {
+  if (!samplers) throw status_error(LLMI_E_ARG, "batch_generate_sampled: null pointer (samplers)");
+  batch_loop("batch_generate_sampled", first, slots, pos, B, n_steps, stop, n_stop, samplers, out);
+}
+
+void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* slots, const int32_t* pos, int B,
+                         int n_steps, const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out) {
+  const std::string f = std::string(fn) + ": ";
+  batch_check(fn, first, slots, pos, B, n_steps);
+  if (n_stop < 0 || n_stop > 4) throw status_error(LLMI_E_ARG, f + "at most 4 stop ids (n_stop)");
+  if (n_stop > 0 && !stop) throw status_error(LLMI_E_ARG, f + "null pointer (stop)");
   BatchStops st{};
   st.n = n_stop;
   for (int i = 0; i < n_stop; i++) {
-    if (stop[i] < 0 || stop[i] >= vocab_) throw status_error(LLMI_E_RANGE, "batch_generate: stop id out of range (stop)");
+    if (stop[i] < 0 || stop[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "stop id out of range (stop)");
     st.id[i] = stop[i];
+  }
+  std::vector<SamplerDev> sp;
+  bool any_greedy = false;
+  if (samplers) {
+    sp.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+      try {
+        validate_sampler(samplers[b]);
+      } catch (const status_error& e) {
+        throw status_error(e.code, f + e.what() + " (samplers[" + std::to_string(b) + "])");
+      }
+      sp[(size_t)b] = SamplerDev{samplers[b].temperature, samplers[b].top_k == 0 ? LLMI_SAMPLE_MAX_K : samplers[b].top_k,
+                                 samplers[b].top_p, 0, samplers[b].seed};
+      any_greedy = any_greedy || samplers[b].temperature == 0.0f;
+    }
+    int ept = 0;
+    if (sample_groups(vocab_, &ept) == 0) throw status_error(LLMI_E_ARG, f + "vocabulary over 1,048,576 rows");
   }
   ensure_usable();
   if (n_steps == 0) return;
   hipStream_t s = stream_;
-  const int E = hp_.n_embd;
   if ((size_t)n_steps * B > bt_ring_cap_) {  // grow-only, as the prefill's chunk buffers
     bt_ring_cap_ = (size_t)n_steps * B;
     bt_ring_ = dalloc<int32_t>(bt_ring_cap_);
+  }
+  if (samplers) {
+    if (!bt_samplers_) bt_samplers_ = dalloc<SamplerDev>(LLMI_SEQ_MAX);
+    ensure_batch_logits(B, true);
+    h2d(bt_samplers_, sp.data(), (size_t)B * sizeof(SamplerDev));
   }
   std::vector<SeqRow> rows((size_t)B);
   std::vector<int> row0;
@@ -268,15 +327,60 @@ void Session::batch_generate(const int32_t* first, const int32_t* slots, const i
   // every step's launches are enqueued at once: tokens, positions, the ids and the stop flags stay on the device
   // (max_pos + i bounds the longest live row: it only decides whether the attention's merge is launched)
   for (int i = 0; i < n_steps; i++) {
-    batch_step(B, max_pos + i, true, i == 0 ? row0 : std::vector<int>());
-    if (i + 1 == n_steps)  // time_kernel(10): the last step's rows as it ran them (pos -1: ended before it)
+    batch_step(B, max_pos + i, true, i == 0 ? row0 : std::vector<int>(), !samplers || any_greedy);
+    if (i + 1 == n_steps)  // time_kernel(10) / (11): the last step's rows as it ran them (pos -1: ended before it)
       LLMI_HIP(hipMemcpyAsync(rows.data(), bt_rows_, (size_t)B * sizeof(SeqRow), hipMemcpyDeviceToHost, s));
-    launch_batch_feedback(sc_amax_, bt_rows_, bt_tok_, B, st, bt_ring_ + (size_t)i * B, s);
+    if (!samplers) {
+      launch_batch_feedback(sc_amax_, bt_rows_, bt_tok_, B, st, bt_ring_ + (size_t)i * B, s);
+      continue;
+    }
+    // the rows' full logits (forward's, soft-capped), then the sampler's two launches; the second is the feedback
+    batch_logits(B, s);
+    launch_sample_select_rows(bt_logits_, vocab_, B, bt_samplers_, bt_rows_, bt_surv_, s);
+    launch_sample_finalize_rows(bt_surv_, vocab_, B, bt_samplers_, sc_amax_, bt_rows_, bt_tok_, st,
+                                bt_ring_ + (size_t)i * B, true, s);
   }
   LLMI_HIP(hipMemcpyAsync(out, bt_ring_, (size_t)n_steps * B * 4, hipMemcpyDeviceToHost, s));
   LLMI_HIP(hipStreamSynchronize(s));
   bt_last_rows_ = rows;
+  if (samplers) {
+    bt_samp_B_ = B;
+    bt_samp_rows_ = rows;
+  }
   check_device_error();
+}
+
+// time_kernel(11): the multi-row logits GEMV + select + finalize (no feedback) over the most recent sampled batch
+// step's rows, with that call's samplers; the final-norm rows are whatever sc_x16_ holds now
+void Session::time_batch_sampling(int reps, double* us, double* bytes) {
+  *us = *bytes = 0.0;
+  const int B = bt_samp_B_, E = hp_.n_embd;
+  if (B == 0 || reps <= 0) return;
+  hipStream_t s = stream_;
+  h2d(bt_trows_, bt_samp_rows_.data(), (size_t)B * sizeof(SeqRow));
+  const int rb = logits_rows_rb(E);
+  const BatchStops st{};
+  std::vector<hipEvent_t> ev(2 * (size_t)reps);
+  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+  LLMI_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < reps; r++) {
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+    batch_logits(B, s);
+    launch_sample_select_rows(bt_logits_, vocab_, B, bt_samplers_, bt_trows_, bt_surv_, s);
+    launch_sample_finalize_rows(bt_surv_, vocab_, B, bt_samplers_, sc_amax_, bt_trows_, bt_tok_, st, bt_ring_, false, s);
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
+  }
+  LLMI_HIP(hipStreamSynchronize(s));
+  double tot = 0;
+  for (int r = 0; r < reps; r++) {
+    float ms = 0;
+    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
+    tot += ms;
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  *us = tot * 1000.0 / reps;
+  const int reads = rb ? (B + rb - 1) / rb : B;
+  *bytes = (double)reads * (double)logits_w_.bytes + (double)B * vocab_ * 4.0;
 }
 
 void Session::time_batch_attn(int reps, double* us, double* bytes) {

@@ -7,6 +7,7 @@ device session of include/llmi.h.
     m.set_sampler(temperature=1.0, top_k=64, top_p=0.95, seed=1)   # ... or seeded sampling in the same loop
     m.reserve_sequences(8)                # KV slots: several sequences per step
     ids = m.batch_generate(firsts, slots, positions, n)   # int32 [n, B], greedy, on device
+    ids = m.batch_generate(firsts, slots, positions, n, samplers=dict(temperature=1.0, top_k=64, seed=1))  # sampled
 """
 from __future__ import annotations
 
@@ -48,6 +49,37 @@ class TPGroup:
 
     def __del__(self):
         self.close()
+
+
+SAMPLER_KEYS = ("temperature", "top_k", "top_p", "seed")  # Model.set_sampler's keywords
+
+
+def normalize_samplers(samplers, B: int):
+    """Model.batch_generate's `samplers` argument as None (the greedy call) or a list of B entries, each None (a
+    greedy row) or a dict with every one of set_sampler's keywords (its defaults filled in).  One dict applies to
+    every row; a sequence must have B entries (ValueError otherwise, as for an unknown keyword or no temperature)."""
+    if samplers is None:
+        return None
+
+    def one(sp):
+        if sp is None:
+            return None
+        if not isinstance(sp, dict):
+            raise ValueError("samplers: each entry is a dict of set_sampler's keywords or None")
+        extra = set(sp) - set(SAMPLER_KEYS)
+        if extra:
+            raise ValueError(f"samplers: unknown keyword(s) {sorted(extra)}")
+        if sp.get("temperature") is None:
+            raise ValueError("samplers: a sampler needs a temperature (None entry: a greedy row)")
+        return dict(temperature=float(sp["temperature"]), top_k=int(sp.get("top_k", 0)),
+                    top_p=float(sp.get("top_p", 1.0)), seed=int(sp.get("seed", 0)))
+
+    if isinstance(samplers, dict):
+        return [one(samplers) for _ in range(B)]
+    sps = [one(sp) for sp in samplers]
+    if len(sps) != B:
+        raise ValueError(f"samplers: {len(sps)} entries for {B} rows")
+    return sps
 
 
 @dataclass
@@ -202,14 +234,26 @@ class Model:
         return BatchResult(am, lse, lg)
 
     def batch_generate(self, first: Sequence[int], slots: Sequence[int], pos: Sequence[int], n_steps: int,
-                       stop: Sequence[int] = ()) -> np.ndarray:
+                       stop: Sequence[int] = (), samplers=None) -> np.ndarray:
         """llmi_session_batch_generate: the greedy loop for B rows on the device; returns int32 [n_steps, B].  A row
-        that emits one of `stop` (at most 4 ids) keeps that id, then -1, and appends nothing more to its slot."""
+        that emits one of `stop` (at most 4 ids) keeps that id, then -1, and appends nothing more to its slot.
+        samplers (llmi_session_batch_generate_sampled): one dict of set_sampler's keywords
+        for every row, or a sequence of B dicts / None entries (None: a greedy row); each sampled row draws its ids
+        by seeded temperature / top-k / top-p sampling at its own positions, inside the same device loop."""
         t, sl, p = self._batch_rows(first, slots, pos)
         st = np.ascontiguousarray(stop, np.int32).reshape(-1)
         out = np.zeros((max(n_steps, 1), max(t.size, 1)), np.int32)
-        check(lib().llmi_session_batch_generate(self.h, ptr(t), ptr(sl), ptr(p), t.size, n_steps,
-                                                ptr(st) if st.size else None, st.size, ptr(out)))
+        sps = normalize_samplers(samplers, t.size)
+        if sps is None:
+            check(lib().llmi_session_batch_generate(self.h, ptr(t), ptr(sl), ptr(p), t.size, n_steps,
+                                                    ptr(st) if st.size else None, st.size, ptr(out)))
+            return out[:n_steps]
+        arr = (Sampler * max(len(sps), 1))()
+        for b, sp in enumerate(sps):  # a greedy row: temperature 0
+            arr[b] = Sampler(0.0, 0, 1.0, 0) if sp is None else Sampler(sp["temperature"], sp["top_k"], sp["top_p"],
+                                                                       sp["seed"] & 0xFFFFFFFFFFFFFFFF)
+        check(lib().llmi_session_batch_generate_sampled(self.h, ptr(t), ptr(sl), ptr(p), t.size, n_steps,
+                                                        ptr(st) if st.size else None, st.size, arr, ptr(out)))
         return out[:n_steps]
 
     def enqueue(self, first: int, pos: int, n_steps: int) -> None:

@@ -218,6 +218,26 @@ def score_rows(x16, w16, targets=None, softcap: float = 0.0):
     return ScoreResult(lp, lse, am, tg if tg is not None else np.full(T, -1, np.int32))
 
 
+def logits_rows_rb(E: int) -> int:
+    """llmi_logits_rows_rb: the activation rows that share one read of the table in logits_rows at width E (0: the
+    width is not supported).  No GPU work."""
+    return int(lib().llmi_logits_rows_rb(int(E)))
+
+
+def logits_rows(x16, w16, softcap: float = 0.0) -> np.ndarray:
+    """llmi_logits_rows: the multi-row F16 logits GEMV alone.  x16 [T][E] and w16 [V][E] as
+    float16 (or their uint16 bits); returns float32 [T][V] whose row t carries the bits of the fast F16
+    mat_vec_mul of w16 with x16[t] (then cap tanh(l / cap) when softcap > 0).  E % 128 != 0 or E > 6144 raises
+    (LLMI_E_SIZE)."""
+    x, w = _f16_bits(x16), _f16_bits(w16)
+    if x.ndim != 2 or w.ndim != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError("logits_rows: x16 [T][E] and w16 [V][E]")
+    T, E = x.shape
+    out = np.zeros((T, w.shape[0]), np.float32)
+    check(lib().llmi_logits_rows(ptr(x), ptr(w), T, w.shape[0], E, float(softcap), ptr(out)))
+    return out
+
+
 class DeviceWeight:
     """A GGUF weight uploaded once (llmi_weight_create); multiply many times."""
 
