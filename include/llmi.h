@@ -200,9 +200,37 @@ int llmi_session_batch_forward(llmi_session* s, const int32_t* tokens, const int
 /* Greedy loop on the device, no host round trip between steps: step i feeds row b's arg-max back as its next token
  * at pos[b] + i + 1.  out[i * B + b] = row b's id after step i.  stop (n_stop <= 4 ids, may be NULL): once row b
  * emits one, that entry is the stop id, every later entry of row b is -1, and row b appends nothing at or past
- * the position the stop id would have taken (main.cpp:196's break, per row).  pos[b] + n_steps <= max_ctx. */
+ * the position the stop id would have taken (main.cpp:196's break, per row).  pos[b] + n_steps <= max_ctx.
+ * (Prompts and several tokens of one sequence per step: llmi_session_batch_extend below.) */
 int llmi_session_batch_generate(llmi_session* s, const int32_t* first, const int32_t* slots, const int32_t* pos,
                                 int B, int n_steps, const int32_t* stop, int n_stop, int32_t* out);
+
+/* Ragged batch steps: one step over a list of spans.  Span i runs n_tokens consecutive tokens
+ * of slot `slot` at positions pos .. pos + n_tokens - 1 (appends their K/V there, each token attending keys 0 .. its own
+ * position of that slot); `tokens` is the spans' tokens concatenated.  A prompt chunk, one decode row (n_tokens = 1:
+ * exactly llmi_session_batch_forward's row) and n draft tokens to verify are all spans, and share the step's one pass
+ * over the weights.  Outputs are compacted in span order: one entry for a LLMI_SPAN_LAST span (its last token), n_tokens
+ * for a LLMI_SPAN_ALL span, none for a LLMI_SPAN_NONE span; argmax / lse (may be NULL) from the fused scorer run over
+ * the output rows only, logits ([n_out][vocab], may be NULL) from the multi-row F16 logits GEMV.  A call whose spans
+ * are all LLMI_SPAN_NONE runs no final norm, no scorer and no GEMV.
+ * Row contract (extends the one above, no tolerance): if K/V rows 0..pos-1 of the slot were written by the batched
+ * prefill, by batch steps or by earlier spans for x[0..pos), then for every token row at position p of a span running
+ * x[pos..pos+n), an output row's argmax / lse are the last entries of llmi_session_score(x[0..p]) and its logits those
+ * of llmi_session_forward(x[0..p], 0) on a fresh single-sequence session, bit for bit -- whatever the other spans, the
+ * split of the sequence into spans and calls, the slots and the span order.  The K/V rows pos..pos+n-1 left in the
+ * slot are the bits llmi_session_forward(x[0..pos+n), 0) leaves in slot 0; rows at and past pos + n are not touched, and
+ * a later span that starts below a slot's previous end simply overwrites (how rejected draft tokens are dropped).
+ * (The single-sequence session's own bits are meant as it computes them for the same token list: an output row at
+ * position 0 is its one-token decode step -- scored like llmi_session_score scores position 0 of a one-token or of a
+ * longer prompt -- and where the batched prefill picks its GEMM by the launch's token rows, the step's row count and
+ * the reference prompt's chunk must fall on the same side of that switch: DESIGN.md section 14.1.)
+ * Checks: sessions as llmi_session_seq_reserve; 1 <= n_spans <= n_seq, a slot at most once per call, n_tokens >= 1,
+ * the sum of n_tokens <= LLMI_BATCH_TOKENS_MAX, pos >= 0, pos + n_tokens <= max_ctx. */
+#define LLMI_BATCH_TOKENS_MAX 512          /* token rows per call: the prefill's default chunk */
+enum { LLMI_SPAN_LAST = 0, LLMI_SPAN_ALL = 1, LLMI_SPAN_NONE = 2 };
+typedef struct { int32_t slot, pos, n_tokens, out; } llmi_span;   /* 16 bytes */
+int llmi_session_batch_extend(llmi_session* s, const int32_t* tokens, const llmi_span* spans, int n_spans,
+                              float* logits, int32_t* argmax, float* lse);
 
 /* op level, host pointers, synchronous: the fused scorer alone.  x16: [T][E] f16 bits, w16: [V][E] f16 bits
  * (row-major), softcap <= 0: none.  E % 16 == 0, else LLMI_E_SIZE. */
@@ -372,7 +400,11 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *  11 = the sampled batch loop's token selection over the most recent sampled batch step's rows: the multi-row
  *       logits GEMV, the sampler's select and finalize launches (no feedback); bytes = table reads
  *       (ceil(B / llmi_logits_rows_rb(n_embd))) x the F16 table plus the B x vocab f32 logits (0 / 0 before any
- *       sampled batch step).
+ *       sampled batch step);
+ *  12 = the span attention launch (+ its merge) of the most recent llmi_session_batch_extend step, one pass over
+ *       the layers (with LLMI_BATCH_SPAN_ROWS=1 in the environment at that call: the per-token form the step ran);
+ *       bytes = the K and V rows 0..last position of every query block of that step, counted once per block, of one
+ *       layer (0 / 0 before any such step).
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

@@ -66,8 +66,17 @@ SAMPLE_MAX_K = 256
 SEQ_MAX = 64  # LLMI_SEQ_MAX: KV slots of one session
 
 
+BATCH_TOKENS_MAX = 512  # LLMI_BATCH_TOKENS_MAX: token rows of one batch_extend call
+SPAN_LAST, SPAN_ALL, SPAN_NONE = 0, 1, 2  # llmi_span.out
+
+
 class Sampler(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
+
+
+class Span(C.Structure):
+    """llmi_span: n_tokens consecutive tokens of a slot, the first at position pos; out: SPAN_LAST / _ALL / _NONE."""
+    _fields_ = [("slot", C.c_int32), ("pos", C.c_int32), ("n_tokens", C.c_int32), ("out", C.c_int32)]
 
 
 _lib = None
@@ -105,6 +114,7 @@ _SIGS = {
     "llmi_session_seq_reserve": (C.c_int, [_vp, C.c_int]),
     "llmi_session_seq_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "llmi_session_batch_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "llmi_session_batch_extend": (C.c_int, [_vp, _vp, C.POINTER(Span), C.c_int, _vp, _vp, _vp]),
     "llmi_session_batch_generate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "llmi_session_batch_generate_sampled": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
                                                       C.POINTER(Sampler), _vp]),

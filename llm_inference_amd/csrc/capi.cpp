@@ -463,6 +463,16 @@ int llmi_session_batch_forward(llmi_session* s, const int32_t* tokens, const int
   });
 }
 
+int llmi_session_batch_extend(llmi_session* s, const int32_t* tokens, const llmi_span* spans, int n_spans,
+                              float* logits, int32_t* argmax, float* lse) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "batch_extend: null pointer");
+    if (!tokens) throw status_error(LLMI_E_ARG, "batch_extend: null pointer (tokens)");
+    if (!spans) throw status_error(LLMI_E_ARG, "batch_extend: null pointer (spans)");
+    s->s->batch_extend(tokens, spans, n_spans, logits, argmax, lse);
+  });
+}
+
 int llmi_session_batch_generate(llmi_session* s, const int32_t* first, const int32_t* slots, const int32_t* pos,
                                 int B, int n_steps, const int32_t* stop, int n_stop, int32_t* out) {
   return guard([&] {

@@ -1498,7 +1498,11 @@ __device__ __forceinline__ void attn_emit(const PrefillAttn& a, const v16f (&o)[
 // MS: the multi-sequence decode form (PrefillAttn::rows): grid.y counts rows, not query blocks -- row b is the
 // single-sequence launch's T = 1 at pos0 = rows[b].pos on its slot's caches, instruction for instruction (lane r of
 // the 32 query columns holds the one query again; only column 0 is merged into a partial or emitted)
-template <int HD, int G, int S, bool MS = false>
+// SP: the span form (PrefillAttn::blocks): grid.y counts the table's query blocks -- entry i is
+// the single-sequence launch's query block of blocks[i].n tokens at pos0 = blocks[i].pos on its slot's caches,
+// instruction for instruction (columns past n repeat the last query, as a prompt's last block does; they write no
+// partial and no output)
+template <int HD, int G, int S, bool MS = false, bool SP = false>
 __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAttn a, int T) {
   constexpr int U = HD / 8;                // 16-B units per cache row
   constexpr int SWM = U < 16 ? U - 1 : 15;  // swizzle mask (units)
@@ -1514,7 +1518,7 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, h = lane >> 5;
   const int g = w % G, sp = w / G;
   // heaviest (last) query blocks first: dispatch order is a speed matter only
-  const int hk = blockIdx.x, qb = MS ? blockIdx.y : gridDim.y - 1 - blockIdx.y, hq = hk * G + g;
+  const int hk = blockIdx.x, qb = (MS || SP) ? blockIdx.y : gridDim.y - 1 - blockIdx.y, hq = hk * G + g;
   int tok0 = qb * 32, pos0 = a.pos0, otok0 = tok0;  // otok0: the token row of query column 0
   const uint16_t *kc = a.k_cache, *vc = a.v_cache;
   if constexpr (MS) {
@@ -1527,7 +1531,17 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
     kc = a.kv_tab[2 * sr.slot];
     vc = a.kv_tab[2 * sr.slot + 1];
   }
-  const int qtok = MS ? qb : min(tok0 + r, T - 1);
+  if constexpr (SP) {
+    const AttnBlock e = a.blocks[qb];
+    if (e.pos < 0) return;  // whole work-group, before any barrier
+    T = e.n;
+    tok0 = 0;
+    otok0 = e.tok0;
+    pos0 = e.pos;
+    kc = a.kv_tab[2 * e.slot];
+    vc = a.kv_tab[2 * e.slot + 1];
+  }
+  const int qtok = MS ? qb : SP ? otok0 + min(r, T - 1) : min(tok0 + r, T - 1);
   const int qpos = pos0 + tok0 + r;                       // this lane's query position
   const int last_pos = pos0 + min(tok0 + 32, T) - 1;     // the block's last query
   const int first_pos = pos0 + tok0;
@@ -1666,6 +1680,7 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
   if (nks > 1) {  // this work-group's partial (m, l, O^T); prefill_attn_merge_kernel combines them
     float* pp = a.part + (((size_t)hq * gridDim.y + qb) * KS + ks) * (64 * (HD / 2 + 2));
     if (MS && r != 0) return;  // one query: columns 1.. repeat it and the merge never reads them
+    if (SP && r >= T) return;  // columns past the block's tokens likewise
     pp[lane] = m_run;
     pp[64 + lane] = l_run;
 #pragma unroll
@@ -1686,10 +1701,10 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
 // head) -- rescales every partial against their maximum and sums them in split order, then writes the outputs
 // as the attention kernel does.  Spread over the chip: the partials of one query block are read by HD / 32
 // work-groups at once rather than by the one work-group that counted in last (round 3, first cut: 26.8 us).
-template <int HD, int NI, bool MS = false>
+template <int HD, int NI, bool MS = false, bool SP = false>
 __global__ __launch_bounds__(64) void prefill_attn_merge_kernel(PrefillAttn a, int T, int S) {
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
-  const int hq = blockIdx.x, nqb = gridDim.y, qb = MS ? blockIdx.y : nqb - 1 - blockIdx.y, i0 = blockIdx.z * NI;
+  const int hq = blockIdx.x, nqb = gridDim.y, qb = (MS || SP) ? blockIdx.y : nqb - 1 - blockIdx.y, i0 = blockIdx.z * NI;
   int tok0 = qb * 32, pos0 = a.pos0, otok0 = tok0;
   if constexpr (MS) {  // row qb's one query (prefill_attn_mfma_kernel<.., MS>): lanes 0 and 32 hold it
     const SeqRow sr = a.rows[qb];
@@ -1698,6 +1713,14 @@ __global__ __launch_bounds__(64) void prefill_attn_merge_kernel(PrefillAttn a, i
     tok0 = 0;
     otok0 = qb;
     pos0 = sr.pos;
+  }
+  if constexpr (SP) {  // entry qb's n queries (prefill_attn_mfma_kernel<.., SP>): lanes r and r + 32, r < n, hold them
+    const AttnBlock e = a.blocks[qb];
+    if (e.pos < 0 || r >= e.n) return;
+    T = e.n;
+    tok0 = 0;
+    otok0 = e.tok0;
+    pos0 = e.pos;
   }
   const int last_pos = pos0 + min(tok0 + 32, T) - 1;
   const int n_rounds = (last_pos / 32 + 1 + S - 1) / S, KS = a.ks, nks = min(KS, n_rounds);
@@ -2045,20 +2068,20 @@ void launch_prefill_qk(const PrefillQK& a, int T, hipStream_t s) {
   LLMI_HIP(hipGetLastError());
 }
 
-// The MFMA attention launch for GQA group G, single-sequence (MS false) or multi-sequence form: ONE table of the
-// key splits per work-group for both, so a batch row cannot merge other splits than the single-sequence launch
-// (the row contract).  S (LDS: two rounds of S tiles, and the merge) depends on head_dim only
+// The MFMA attention launch for GQA group G, single-sequence (MS false), multi-sequence (MS) or span (SP) form: ONE
+// table of the key splits per work-group for all three, so a batch row or a span's query block cannot merge other
+// splits than the single-sequence launch (the row contract, DESIGN.md sections 12 and 14).  S (LDS: two rounds of S tiles, and the merge) depends on head_dim only
 // but for G = 4 at head_dim 128, so a tensor-parallel rank (fewer heads per kv head: smaller G) merges the same
 // splits as the whole model (bit-identical).  head_dim 256 at G 1 / 4 spills some of the 128 O^T + 64 Q^T registers
 // (correct, slower).  Returns S, 0 for a group it does not cover.
-template <int HD, bool MS>
+template <int HD, bool MS, bool SP = false>
 static int launch_attn_mfma(const PrefillAttn& a, int T, const dim3& grid, hipStream_t s) {
   constexpr int S4 = HD >= 256 ? 2 : 4;
   constexpr int SG4 = HD == 128 ? 2 : S4;
   switch (a.n_head / a.n_head_kv) {
-    case 1: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 1, S4, MS>), grid, dim3(64 * S4), 0, s, a, T); return S4;
-    case 2: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 2, S4, MS>), grid, dim3(128 * S4), 0, s, a, T); return S4;
-    case 4: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 4, SG4, MS>), grid, dim3(256 * SG4), 0, s, a, T); return SG4;
+    case 1: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 1, S4, MS, SP>), grid, dim3(64 * S4), 0, s, a, T); return S4;
+    case 2: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 2, S4, MS, SP>), grid, dim3(128 * S4), 0, s, a, T); return S4;
+    case 4: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 4, SG4, MS, SP>), grid, dim3(256 * SG4), 0, s, a, T); return SG4;
     default: return 0;
   }
 }
@@ -2083,8 +2106,29 @@ static void attn_rows(const PrefillAttn& a, int T, hipStream_t s) {
   }
 }
 
+// The span form: a.n_blocks query blocks of up to 32 consecutive tokens, each on its own slot at its own position
+// (PrefillAttn::blocks).  Grid (kv head, block, key split); the spare work-groups of a short block and the merge
+// as in attn_rows, a.pos0 the longest block's last position.  Same sizes and outputs as attn_rows.
+template <int HD>
+static void attn_spans(const PrefillAttn& a, hipStream_t s) {
+  if constexpr (HD < 128) {
+    throw std::runtime_error("prefill_attn: the span form needs head_dim 128 or 256");
+  } else {
+    if (!a.kv_tab || getenv("LLMI_PREFILL_ATTN_V1") || a.q8k || !a.part || a.ks < 1 || a.ks > PREFILL_ATTN_KS_MAX ||
+        a.n_blocks < 1)
+      throw std::runtime_error("prefill_attn: the span form needs the MFMA kernel, Q8_0 / f16 outputs, the partial "
+                               "scratch and a block table");
+    const int S = launch_attn_mfma<HD, false, true>(a, 0, dim3(a.n_head_kv, a.n_blocks, a.ks), s);
+    if (!S) throw std::runtime_error("prefill_attn: the span form needs GQA group 1, 2 or 4");
+    if (a.ks > 1 && a.pos0 / 32 + 1 > S)
+      hipLaunchKernelGGL((prefill_attn_merge_kernel<HD, 1, false, true>), dim3(a.n_head, a.n_blocks, HD / 32), dim3(64),
+                         0, s, a, 0, S);
+  }
+}
+
 template <int HD>
 static void attn_g(const PrefillAttn& a, int T, hipStream_t s) {
+  if (a.blocks) return attn_spans<HD>(a, s);
   if (a.rows) return attn_rows<HD>(a, T, s);
   const int G = a.n_head / a.n_head_kv;
   if ((a.x16 || a.q8k) && (getenv("LLMI_PREFILL_ATTN_V1") || (G != 1 && G != 2 && G != 4)))

@@ -1028,8 +1028,10 @@ bool Session::prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16)
 // the session's own cache (prefill_run).  rows non-null: row b is position rows[b].pos of KV slot rows[b].slot
 // (batch_step; p0 = the longest row's position, a bound for the attention's merge launch) -- the q/k and attention
 // launches take their multi-sequence forms, every other launch is row-independent and runs as it is.
+// blocks non-null (batch_extend): the rows are spans of consecutive positions, the attention takes its span form over
+// these query blocks (p0 = the longest block's last position).
 void Session::prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, bool last_chunk, bool f16_all,
-                             const SeqRow* rows) {
+                             const SeqRow* rows, const AttnBlock* blocks, int n_blocks) {
   hipStream_t s = stream_;
   const int E = hp_.n_embd, F = hp_.n_ff;
   // attention key splits across work-groups: a constant (never a function of the heads per rank), so tensor-
@@ -1148,13 +1150,17 @@ void Session::prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, 
     at.x16stride = X16;
     at.q8k = q8k;
     at.ks = pf_attn_ks_;
-    at.part = rows ? bt_apart_ : pf_apart_;
+    at.part = blocks ? bx_apart_ : rows ? bt_apart_ : pf_apart_;
     at.rows = rows;
     at.kv_tab = qk.kv_tab;
-    launch_prefill_attn(at, Tq, s);
-    if (rows) {  // time_kernel(10)
-      if ((int)bt_last_attn_.size() != hp_.n_layer) bt_last_attn_.resize((size_t)hp_.n_layer);
-      bt_last_attn_[(size_t)l] = at;
+    at.blocks = blocks;
+    at.n_blocks = n_blocks;
+    if (rows) launch_batch_attn(at, Tq, s);
+    else launch_prefill_attn(at, Tq, s);
+    if (rows) {  // time_kernel(10), or (a batch_extend step) time_kernel(12)
+      std::vector<PrefillAttn>& last = bx_step_ ? bx_last_attn_ : bt_last_attn_;
+      if ((int)last.size() != hp_.n_layer) last.resize((size_t)hp_.n_layer);
+      last[(size_t)l] = at;
     }
     if (!tp_rep_attn_) xgather(nh_ * hd);
     tap("pf_q", l, pf_q_, (size_t)T * nh_ * hd * 2, s);
@@ -2347,6 +2353,7 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
   }
   if (which == 10) return time_batch_attn(reps, us, bytes);  // (session_batch.cpp)
   if (which == 11) return time_batch_sampling(reps, us, bytes);
+  if (which == 12) return time_extend_attn(reps, us, bytes);
   if (which == 9) {  // the fused scorer's two launches over the most recently scored chunk (its rows are still there)
     *us = *bytes = 0.0;
     if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;

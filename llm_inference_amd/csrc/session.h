@@ -91,6 +91,9 @@ class Session {
                      int32_t* argmax, float* lse);
   void batch_generate(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                       const int32_t* stop, int n_stop, int32_t* out);
+  // ragged batch steps: spans of consecutive tokens, each on its own slot
+  void batch_extend(const int32_t* tokens, const llmi_span* spans, int n_spans, float* logits, int32_t* argmax,
+                    float* lse);
   // per-row seeded sampling inside the batch loop; samplers: B entries
   void batch_generate_sampled(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                               const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);
@@ -126,8 +129,9 @@ class Session {
   bool prefill_f16_ok() const;  // the batched prefill's activations as f16 rows (GEMM v7 / v6)
   bool prefill_run(const int32_t* tokens, int n, int pos, bool allow_f16);  // true: ran the f16 path
   // one chunk's launches through every layer (prefill_run's consecutive positions, or batch_step's rows)
+  // blocks non-null (with rows: one SeqRow per token row): a batch_extend step, its attention in the span form
   void prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, bool last_chunk, bool f16_all,
-                      const SeqRow* rows);
+                      const SeqRow* rows, const AttnBlock* blocks = nullptr, int n_blocks = 0);
   void gather_cols(void* buf, size_t pitch_b, size_t slice_b, int T, hipStream_t s);
   void ensure_prefill_buffers(int cap);
   void record_layers(hipStream_t s, bool x_q8);
@@ -343,7 +347,8 @@ class Session {
                   const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);
   // final-norm rows sc_x16_[0..B) -> bt_logits_ [B][vocab], soft-capped: the multi-row logits GEMV, or launch_gemv
   // row by row for a table width it does not take
-  void batch_logits(int B, hipStream_t s);
+  // (x16: the rows to read instead of sc_x16_ -- batch_extend's compact block)
+  void batch_logits(int B, hipStream_t s, const uint16_t* x16 = nullptr);
   SamplerDev* bt_samplers_ = nullptr;         // [LLMI_SEQ_MAX] the sampled loop's per-row samplers
   float* bt_logits_ = nullptr;                // [bt_logits_cap_][vocab] grow-only
   unsigned long long* bt_surv_ = nullptr;     // [bt_logits_cap_][SAMPLE_MAX_GROUPS x 256]
@@ -352,6 +357,21 @@ class Session {
   std::vector<SeqRow> bt_samp_rows_;          // ... as it ran them
   void ensure_batch_logits(int B, bool surv);
   void time_batch_sampling(int reps, double* us, double* bytes);
+  // ragged batch steps (llmi_session_batch_extend): a step is a list of spans, its token rows
+  // the spans concatenated
+  SeqRow* bx_rows_ = nullptr;       // [LLMI_BATCH_TOKENS_MAX] one per token row
+  int32_t* bx_tok_ = nullptr;       // [LLMI_BATCH_TOKENS_MAX]
+  AttnBlock* bx_blocks_ = nullptr;  // [LLMI_SEQ_MAX + LLMI_BATCH_TOKENS_MAX / 32] the step's query blocks
+  float* bx_apart_ = nullptr;       // span attention partials [head][block][PREFILL_ATTN_KS_MAX], 32 columns each
+  uint16_t* bx_x16_ = nullptr;      // [LLMI_BATCH_TOKENS_MAX][n_embd] the output rows' final-norm rows, compact
+  bool bx_step_ = false;            // prefill_layers is enqueuing a batch_extend step (its launches go to bx_last_attn_)
+  std::vector<PrefillAttn> bx_last_attn_;  // the most recent batch_extend step's attention launches, per layer
+  std::vector<SeqRow> bx_last_rows_;       // ... its token rows
+  std::vector<AttnBlock> bx_last_blocks_;  // ... and its query blocks (host)
+  // the attention of a multi-sequence step of T rows: one launch, or (per-token form, T > LLMI_SEQ_MAX: bt_apart_
+  // holds that many rows' partials) one per LLMI_SEQ_MAX rows
+  void launch_batch_attn(const PrefillAttn& at, int T, hipStream_t s);
+  void time_extend_attn(int reps, double* us, double* bytes);
 };
 
 }  // namespace llmi

@@ -1,7 +1,9 @@
 // session_batch.cpp -- several sequences per step (llmi_session_seq_* / llmi_session_batch_*).
 // A batch step is the batched prefill's launch sequence over B token rows (Session::prefill_layers), each row a
 // position of its own KV slot, then the scorer's rows; the greedy loop adds one feedback launch per step, the
-// sampled loop (section 13) the rows' full logits and the sampler's two multi-row launches.
+// sampled loop (section 13) the rows' full logits and the sampler's two multi-row launches.  A ragged step
+// (llmi_session_batch_extend, section 14) carries spans of consecutive tokens: prompt chunks and draft tokens beside
+// decode rows, the attention in its span form.
 #include "session.h"
 
 #include <algorithm>
@@ -234,6 +236,213 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
   }
 }
 
+// The attention of a multi-sequence step.  The per-token form's partials (bt_apart_) hold LLMI_SEQ_MAX rows: a span
+// step routed through it (LLMI_BATCH_SPAN_ROWS=1) goes that many rows at a time -- a row's bits do not depend on
+// which launch carries it.
+void Session::launch_batch_attn(const PrefillAttn& at, int T, hipStream_t s) {
+  if (at.blocks || T <= LLMI_SEQ_MAX) return launch_prefill_attn(at, T, s);
+  for (int c0 = 0; c0 < T; c0 += LLMI_SEQ_MAX) {
+    PrefillAttn c = at;
+    c.q += (size_t)c0 * at.n_head * at.head_dim;
+    c.xq += (size_t)c0 * at.xstride;
+    if (c.x16) c.x16 += (size_t)c0 * at.x16stride;
+    c.rows += c0;
+    launch_prefill_attn(c, std::min(LLMI_SEQ_MAX, T - c0), s);
+  }
+}
+
+// A ragged batch step: the batched prefill's launch sequence over the spans' token rows -- the
+// q/k launch with one SeqRow per token row, the attention in its span form (one query block per 32 consecutive
+// tokens of a span) -- then the final norm, the scorer and the logits GEMV over the output rows only.
+void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_spans, float* logits, int32_t* argmax,
+                           float* lse) {
+  const std::string f = "batch_extend: ";
+  if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
+  if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
+  if (n_spans < 1 || n_spans > n_seq_) throw status_error(LLMI_E_RANGE, f + "n_spans must be in 1..n_seq (n_spans)");
+  bool seen[LLMI_SEQ_MAX] = {};
+  int total = 0, n_out_all = 0;
+  std::vector<int> tok_off((size_t)n_spans), out_off((size_t)n_spans);
+  for (int i = 0; i < n_spans; i++) {
+    const llmi_span& sp = spans[i];
+    if (sp.slot < 0 || sp.slot >= n_seq_) throw status_error(LLMI_E_RANGE, f + "slot outside [0, n_seq) (spans.slot)");
+    if (seen[sp.slot]) throw status_error(LLMI_E_ARG, f + "duplicate slot in one call (spans.slot)");
+    seen[sp.slot] = true;
+    if (sp.n_tokens < 1) throw status_error(LLMI_E_ARG, f + "a span needs at least one token (spans.n_tokens)");
+    if (sp.out < LLMI_SPAN_LAST || sp.out > LLMI_SPAN_NONE)
+      throw status_error(LLMI_E_ARG, f + "out must be LLMI_SPAN_LAST, _ALL or _NONE (spans.out)");
+    if (sp.n_tokens > LLMI_BATCH_TOKENS_MAX - total)
+      throw status_error(LLMI_E_RANGE, f + "more than " + std::to_string(LLMI_BATCH_TOKENS_MAX) +
+                                           " token rows in one call (sum of spans.n_tokens)");
+    if (sp.pos < 0 || sp.pos > max_ctx_ - sp.n_tokens)
+      throw status_error(LLMI_E_RANGE, f + "context overflow (spans.pos + n_tokens)");
+    tok_off[(size_t)i] = total;
+    out_off[(size_t)i] = n_out_all;
+    total += sp.n_tokens;
+    n_out_all += sp.out == LLMI_SPAN_ALL ? sp.n_tokens : sp.out == LLMI_SPAN_LAST ? 1 : 0;
+  }
+  for (int t = 0; t < total; t++)
+    if (tokens[t] < 0 || tokens[t] >= vocab_) throw status_error(LLMI_E_RANGE, f + "token id out of range (tokens)");
+  ensure_usable();
+  hipStream_t s = stream_;
+  const int E = hp_.n_embd;
+  if (!bx_rows_) {
+    int maxhd = 0;
+    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
+    const size_t max_blocks = LLMI_SEQ_MAX + LLMI_BATCH_TOKENS_MAX / 32;
+    bx_rows_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
+    bx_tok_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
+    bx_blocks_ = dalloc<AttnBlock>(max_blocks);
+    bx_apart_ = dalloc<float>((size_t)nh_ * max_blocks * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
+    bx_x16_ = dalloc<uint16_t>((size_t)LLMI_BATCH_TOKENS_MAX * E);
+  }
+  if (!bt_apart_) {  // (the per-token form's partials, as batch_step)
+    int maxhd = 0;
+    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
+    bt_apart_ = dalloc<float>((size_t)nh_ * LLMI_SEQ_MAX * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
+  }
+  // A/B, read at the call: the step's attention through the per-token multi-sequence form, one SeqRow per token row
+  // (legal because the q/k launch has appended the step's K/V before it; the same bits)
+  const char* sr_env = getenv("LLMI_BATCH_SPAN_ROWS");
+  const bool span_rows = sr_env && atoi(sr_env) == 1;
+  std::vector<uint16_t> hx;
+  std::vector<int> bad;  // the last step's spans with a non-finite output row
+  // the spans idx[0..n) of the call as one step; results into the caller's arrays at those spans' output entries
+  auto run = [&](const std::vector<int>& idx, bool allow_f16) -> bool {
+    std::vector<SeqRow> rows;
+    std::vector<int32_t> tok;
+    std::vector<AttnBlock> blocks;
+    struct Run {  // a span's output rows: token rows row0 .. row0 + n - 1 -> compact rows o0 .., caller's entries dst ..
+      int span, row0, n, o0, dst;
+    };
+    std::vector<Run> outs;
+    struct Row0 {  // an output row at position 0: compact output row, bt_row0_ entry, a one-token span
+      int o, k;
+      bool single;
+    };
+    std::vector<Row0> r0;
+    int max_pos = 0, n_out = 0;
+    for (int k = 0; k < (int)idx.size(); k++) {
+      const llmi_span& sp = spans[idx[(size_t)k]];
+      const int32_t* st = tokens + tok_off[(size_t)idx[(size_t)k]];
+      const int t0 = (int)rows.size();
+      for (int j = 0; j < sp.n_tokens; j++) {
+        rows.push_back(SeqRow{sp.slot, sp.pos + j});
+        tok.push_back(st[j]);
+      }
+      for (int j = 0; j < sp.n_tokens; j += 32)
+        blocks.push_back(AttnBlock{t0 + j, std::min(32, sp.n_tokens - j), sp.slot, sp.pos + j});
+      max_pos = std::max(max_pos, sp.pos + sp.n_tokens - 1);
+      if (sp.out == LLMI_SPAN_NONE) continue;
+      const int n = sp.out == LLMI_SPAN_ALL ? sp.n_tokens : 1;
+      outs.push_back(Run{idx[(size_t)k], t0 + sp.n_tokens - n, n, n_out, out_off[(size_t)idx[(size_t)k]]});
+      // an output row at position 0 is forward's / score's one-token step (batch_row0); the step below then rewrites
+      // the slot's K / V row 0 with the batched prefill's bits.  As score() does it: a one-token span's lse / arg-max
+      // are that step's (the f64 row reduce, score's one-token call); a longer span hands the step's final-norm row
+      // to the fused scorer with its other rows (score_chunk's sc_row0_)
+      if (sp.pos + sp.n_tokens - n == 0) {
+        batch_row0(st[0], sp.slot, k);
+        r0.push_back(Row0{n_out, k, sp.n_tokens == 1});
+      }
+      n_out += n;
+    }
+    const int T = (int)rows.size();
+    // heaviest query blocks first: dispatch order is a speed matter only
+    std::stable_sort(blocks.begin(), blocks.end(),
+                     [](const AttnBlock& a, const AttnBlock& b) { return a.pos + a.n > b.pos + b.n; });
+    h2d(bx_rows_, rows.data(), (size_t)T * sizeof(SeqRow));
+    h2d(bx_tok_, tok.data(), (size_t)T * 4);
+    h2d(bx_blocks_, blocks.data(), blocks.size() * sizeof(AttnBlock));
+    ensure_prefill_buffers(T);
+    const bool f16_all = allow_f16 && prefill_f16_ok();
+    bx_step_ = true;
+    try {  // the last layer over every row, as batch_step
+      prefill_layers(bx_tok_, T, max_pos, /*trim=*/false, /*last_chunk=*/false, f16_all, bx_rows_,
+                     span_rows ? nullptr : bx_blocks_, span_rows ? 0 : (int)blocks.size());
+    } catch (...) {
+      bx_step_ = false;
+      throw;
+    }
+    bx_step_ = false;
+    bx_last_rows_ = rows;
+    bx_last_blocks_ = blocks;
+    if (n_out == 0) {  // no final norm, no scorer, no GEMV (and no f16 check, like batch_generate)
+      LLMI_HIP(hipStreamSynchronize(s));
+      check_device_error();
+      return false;
+    }
+    ensure_score_buffers(std::max(n_out, pf_cap_));
+    // the output rows' final-norm rows, compact in span order
+    for (const Run& o : outs)
+      launch_residual_norm_rows16(pf_out_ + (size_t)o.row0 * E, E, L_.back().post_ffw_norm, pf_resid_ + (size_t)o.row0 * E,
+                                  E, out_norm_, bx_x16_ + (size_t)o.o0 * E, E, E, o.n, hp_.eps, s);
+    for (const Row0& p : r0)
+      LLMI_HIP(hipMemcpyAsync(bx_x16_ + (size_t)p.o * E, bt_row0_ + (size_t)p.k * E, (size_t)E * 2,
+                              hipMemcpyDeviceToDevice, s));
+    ScoreArgs a;
+    a.x16 = bx_x16_;
+    a.xstride = E;
+    a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
+    a.T = n_out;
+    a.V = vocab_;
+    a.E = E;
+    a.softcap = hp_.final_softcap;
+    a.targets = nullptr;
+    a.ms = sc_ms_;
+    a.key = sc_key_;
+    a.tl = sc_tl_;
+    a.logprob = sc_lp_;
+    a.lse = sc_lse_;
+    a.argmax = sc_amax_;
+    launch_score_rows(a, s);
+    for (const Row0& p : r0) {  // (batch_row0)
+      if (!p.single) continue;
+      LLMI_HIP(hipMemcpyAsync(sc_lse_ + p.o, bt_r0_lse_ + p.k, 4, hipMemcpyDeviceToDevice, s));
+      LLMI_HIP(hipMemcpyAsync(sc_amax_ + p.o, bt_r0_amax_ + p.k, 4, hipMemcpyDeviceToDevice, s));
+    }
+    hx.resize((size_t)n_out * E);
+    std::vector<int32_t> am((size_t)n_out);
+    std::vector<float> ls((size_t)n_out);
+    LLMI_HIP(hipMemcpyAsync(hx.data(), bx_x16_, hx.size() * 2, hipMemcpyDeviceToHost, s));
+    LLMI_HIP(hipMemcpyAsync(am.data(), sc_amax_, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
+    LLMI_HIP(hipMemcpyAsync(ls.data(), sc_lse_, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
+    if (logits) {  // forward's logits GEMV on the compact rows, LLMI_SEQ_MAX of them at a time (bt_logits_'s size)
+      ensure_batch_logits(std::min(n_out, LLMI_SEQ_MAX), false);
+      for (const Run& o : outs)
+        for (int c0 = 0; c0 < o.n; c0 += LLMI_SEQ_MAX) {
+          const int n = std::min(LLMI_SEQ_MAX, o.n - c0);
+          batch_logits(n, s, bx_x16_ + (size_t)(o.o0 + c0) * E);
+          LLMI_HIP(hipMemcpyAsync(logits + (size_t)(o.dst + c0) * vocab_, bt_logits_, (size_t)n * vocab_ * 4,
+                                  hipMemcpyDeviceToHost, s));
+        }
+    }
+    LLMI_HIP(hipStreamSynchronize(s));
+    check_device_error();
+    for (const Run& o : outs)
+      for (int j = 0; j < o.n; j++) {
+        if (argmax) argmax[o.dst + j] = am[(size_t)(o.o0 + j)];
+        if (lse) lse[o.dst + j] = ls[(size_t)(o.o0 + j)];
+      }
+    bad.clear();
+    for (const Run& o : outs)
+      for (size_t i = (size_t)o.o0 * E; i < (size_t)(o.o0 + o.n) * E; i++)
+        if (!f16_finite(hx[i])) {
+          bad.push_back(o.span);
+          break;
+        }
+    return f16_all;
+  };
+  std::vector<int> all((size_t)n_spans);
+  for (int i = 0; i < n_spans; i++) all[(size_t)i] = i;
+  if (!run(all, true)) return;
+  // the f16 path (Session::prefill's rule, per span): a span with a non-finite output row runs again as a smaller
+  // step on the int8 path, all of its token rows, rewriting the same K / V rows
+  if (!bad.empty()) {
+    pf_f16_redo_++;
+    run(std::vector<int>(bad), false);
+  }
+}
+
 void Session::ensure_batch_logits(int B, bool surv) {  // grow-only, as the prefill's chunk buffers
   if (B > bt_logits_cap_) {
     bt_logits_ = dalloc<float>((size_t)B * vocab_);
@@ -245,13 +454,14 @@ void Session::ensure_batch_logits(int B, bool surv) {  // grow-only, as the pref
   }
 }
 
-void Session::batch_logits(int B, hipStream_t s) {
+void Session::batch_logits(int B, hipStream_t s, const uint16_t* x16) {
   const int E = hp_.n_embd;
+  if (!x16) x16 = sc_x16_;
   if (logits_rows_rb(E) != 0) {
-    launch_gemv_f16_rows(logits_w_, sc_x16_, E, B, bt_logits_, s);
+    launch_gemv_f16_rows(logits_w_, x16, E, B, bt_logits_, s);
   } else {  // one table read per row
     for (int i = 0; i < B; i++) {
-      LLMI_HIP(hipMemcpyAsync(act_.x16, sc_x16_ + (size_t)i * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
+      LLMI_HIP(hipMemcpyAsync(act_.x16, x16 + (size_t)i * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
       launch_gemv(logits_w_, act_, bt_logits_ + (size_t)i * vocab_, GEMV_FAST, s, nullptr);
     }
   }
@@ -405,6 +615,39 @@ void Session::time_batch_attn(int reps, double* us, double* bytes) {
       at.pos0 = max_pos;
       launch_prefill_attn(at, B, s);
     }
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
+  }
+  LLMI_HIP(hipStreamSynchronize(s));
+  double tot = 0;
+  for (int r = 0; r < reps; r++) {
+    float ms = 0;
+    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
+    tot += ms;
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  *us = tot * 1000.0 / reps / NL;
+  *bytes = by / NL;
+}
+
+// time_kernel(12): the attention launches of the most recent batch_extend step as it ran them -- the span form and
+// its merge, or (LLMI_BATCH_SPAN_ROWS=1 at that call) the per-token form over the same token rows
+void Session::time_extend_attn(int reps, double* us, double* bytes) {
+  *us = *bytes = 0.0;
+  const int NL = hp_.n_layer, T = (int)bx_last_rows_.size();
+  if (T == 0 || (int)bx_last_attn_.size() != NL || reps <= 0) return;
+  hipStream_t s = stream_;
+  // (the step's own tables: nothing else writes them)
+  h2d(bx_rows_, bx_last_rows_.data(), (size_t)T * sizeof(SeqRow));
+  h2d(bx_blocks_, bx_last_blocks_.data(), bx_last_blocks_.size() * sizeof(AttnBlock));
+  double by = 0.0;  // K and V rows 0 .. last position of every query block, once per block
+  for (int l = 0; l < NL; l++)
+    for (const auto& b : bx_last_blocks_) by += (double)(b.pos + b.n) * 2.0 * nkv_ * L_[(size_t)l].hd * 2.0;
+  std::vector<hipEvent_t> ev(2 * (size_t)reps);
+  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+  LLMI_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < reps; r++) {
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+    for (int l = 0; l < NL; l++) launch_batch_attn(bx_last_attn_[(size_t)l], T, s);  // (writes the o projection's x only)
     LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
   }
   LLMI_HIP(hipStreamSynchronize(s));

@@ -167,6 +167,11 @@ struct PrefillGemm16 {  // f16 activations [T][xstride elements] (k_prefill.hip 
 struct SeqRow {
   int slot, pos;
 };
+// A query block of a span launch (Session::batch_extend): n (1..32) consecutive tokens of KV
+// slot `slot`, the first at position `pos`, in token rows tok0 .. tok0 + n - 1 of the step.  pos < 0: nothing to do.
+struct AttnBlock {
+  int tok0, n, slot, pos;
+};
 struct PrefillQK {
   const float* qkv = nullptr;  // [T][qkv_stride]
   int qkv_stride = 0, k_off = 0, v_off = 0, n_head = 0, n_head_kv = 0, head_dim = 0;
@@ -202,6 +207,12 @@ struct PrefillAttn {
   // q, the outputs and the partials are indexed by b.  part: [head][row][ks] partials
   const SeqRow* rows = nullptr;
   uint16_t* const* kv_tab = nullptr;
+  // span form (blocks non-null): grid.y counts the n_blocks query blocks of this table, each
+  // the single-sequence launch's query block of blocks[i].n consecutive tokens at pos0 = blocks[i].pos on its slot's
+  // caches; pos0 here = the longest block's last position (a host-side bound for the merge launch).  part:
+  // [head][block][ks] partials.  rows is not read
+  const AttnBlock* blocks = nullptr;
+  int n_blocks = 0;
 };
 // the greedy batch loop's feedback (after the scorer's merge): a live row b takes id = argmax[b] -> out[b]; a stop id
 // ends the row (rows[b].pos = -1), any other id becomes tokens[b] at rows[b].pos + 1.  Ended rows: out[b] = -1

@@ -8,17 +8,19 @@ device session of include/llmi.h.
     m.reserve_sequences(8)                # KV slots: several sequences per step
     ids = m.batch_generate(firsts, slots, positions, n)   # int32 [n, B], greedy, on device
     ids = m.batch_generate(firsts, slots, positions, n, samplers=dict(temperature=1.0, top_k=64, seed=1))  # sampled
+    last = m.prefill_sequences(prompts, slots)            # prompts straight into their slots
+    r = m.batch_extend([chunk, [tok], drafts], [0, 1, 2], [128, 40, 64], out=["none", "last", "all"])  # a ragged step
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, TP_ID_BYTES, TRACE_FN, Sampler,
-                   SessionInfo, SessionOpts, check, lib, ptr)
+from ._lib import (BATCH_TOKENS_MAX, LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, SPAN_ALL,
+                   SPAN_LAST, SPAN_NONE, TP_ID_BYTES, TRACE_FN, Sampler, SessionInfo, SessionOpts, Span, check, lib, ptr)
 from .gguf import GGUFFile
 from .score import ScoreResult, resolve_targets
 
@@ -88,6 +90,84 @@ class BatchResult:
     argmax: np.ndarray            # int32 [B]
     lse: np.ndarray               # float32 [B]
     logits: Optional[np.ndarray]  # float32 [B, vocab] or None
+
+
+@dataclass
+class ExtendResult:
+    """Model.batch_extend: the output rows compacted in span order -- span i's are [offsets[i], offsets[i + 1])."""
+    argmax: np.ndarray            # int32 [n_out]
+    lse: np.ndarray               # float32 [n_out]
+    logits: Optional[np.ndarray]  # float32 [n_out, vocab] or None
+    offsets: np.ndarray           # int64 [n_spans + 1]
+
+
+SPAN_OUT = {"last": SPAN_LAST, "all": SPAN_ALL, "none": SPAN_NONE}
+
+
+def marshal_extend(seqs, slots, pos, out="last"):
+    """Model.batch_extend's arguments as llmi_session_batch_extend takes them: (tokens int32 -- the spans' tokens
+    concatenated, a ctypes array of Span, offsets int64 [n_spans + 1] of the spans' output rows).  out: one of
+    "last" | "all" | "none", or one value per span."""
+    seqs = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in seqs]
+    sl, p = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (slots, pos))
+    outs = [out] * len(seqs) if isinstance(out, str) else list(out)
+    if not (len(seqs) == sl.size == p.size == len(outs)):
+        raise ValueError("seqs, slots, pos and (as a sequence) out must have one entry per span")
+    for o in outs:
+        if o not in SPAN_OUT:
+            raise ValueError(f"out: {o!r} is none of 'last', 'all', 'none'")
+    arr = (Span * max(len(seqs), 1))()
+    offsets = np.zeros(len(seqs) + 1, np.int64)
+    for i, (x, o) in enumerate(zip(seqs, outs)):
+        arr[i] = Span(int(sl[i]), int(p[i]), x.size, SPAN_OUT[o])
+        offsets[i + 1] = offsets[i] + (x.size if o == "all" else 1 if o == "last" else 0)
+    tokens = np.concatenate(seqs).astype(np.int32) if seqs else np.zeros(0, np.int32)
+    return tokens, arr, offsets
+
+
+class PlannedSpan(NamedTuple):
+    """One span of plan_extend_calls: tokens [start, start + n_tokens) of prompt `prompt`, at positions pos .. of its
+    slot; out "last" for the prompt's final span, "none" for every other."""
+    prompt: int
+    slot: int
+    pos: int
+    start: int
+    n_tokens: int
+    out: str
+
+
+def plan_extend_calls(lengths, slots, pos=0, max_tokens=BATCH_TOKENS_MAX):
+    """Model.prefill_sequences' plan: prompts of `lengths` tokens, prompt i into slot slots[i] from position pos (one
+    int, or one per prompt), as a list of batch_extend calls, each a list of PlannedSpan.  A call carries at most
+    max_tokens token rows and a slot at most once; a long prompt is cut into consecutive spans across calls, short
+    ones share a call; in prompt order.  ValueError: an empty prompt, a slot given twice, a negative position."""
+    lengths = [int(n) for n in lengths]
+    slots = [int(s) for s in slots]
+    starts = [int(pos)] * len(lengths) if np.isscalar(pos) else [int(q) for q in pos]
+    if not (len(lengths) == len(slots) == len(starts)):
+        raise ValueError("lengths, slots and pos must have one entry per prompt")
+    if max_tokens < 1:
+        raise ValueError("max_tokens must be at least 1")
+    if any(n < 1 for n in lengths):
+        raise ValueError("an empty prompt has no last token")
+    if len(set(slots)) != len(slots):
+        raise ValueError("each prompt needs a slot of its own")
+    if any(q < 0 for q in starts):
+        raise ValueError("negative position")
+    calls, cur, room = [], [], max_tokens
+    for i, n in enumerate(lengths):
+        done = 0
+        while done < n:
+            if room == 0:
+                calls.append(cur)
+                cur, room = [], max_tokens
+            take = min(n - done, room)
+            cur.append(PlannedSpan(i, slots[i], starts[i] + done, done, take, "last" if done + take == n else "none"))
+            done += take
+            room -= take
+    if cur:
+        calls.append(cur)
+    return calls
 
 
 class Model:
@@ -232,6 +312,38 @@ class Model:
         check(lib().llmi_session_batch_forward(self.h, ptr(t), ptr(sl), ptr(p), t.size,
                                                ptr(lg) if lg is not None else None, ptr(am), ptr(lse)))
         return BatchResult(am, lse, lg)
+
+    def batch_extend(self, seqs, slots: Sequence[int], pos: Sequence[int], out="last",
+                     want_logits: bool = False) -> ExtendResult:
+        """llmi_session_batch_extend: one ragged step -- span i runs the tokens seqs[i] at positions pos[i] .. of
+        slot slots[i]: a prompt chunk, one decode row or draft tokens to verify, all sharing the step's pass over
+        the weights.  out ("last" | "all" | "none", or one per span) selects each span's output rows; every output
+        row carries the bits of score() / forward() of the same prefix on a single-sequence session (DESIGN.md
+        section 14)."""
+        t, arr, offsets = marshal_extend(seqs, slots, pos, out)
+        n_out = int(offsets[-1])
+        am, lse = np.zeros(max(n_out, 1), np.int32), np.zeros(max(n_out, 1), np.float32)
+        lg = np.zeros((n_out, self.vocab), np.float32) if want_logits and n_out else None
+        check(lib().llmi_session_batch_extend(self.h, ptr(t) if t.size else None, arr, len(offsets) - 1,
+                                              ptr(lg) if lg is not None else None, ptr(am) if n_out else None,
+                                              ptr(lse) if n_out else None))
+        if want_logits and lg is None:
+            lg = np.zeros((0, self.vocab), np.float32)
+        return ExtendResult(am[:n_out], lse[:n_out], lg, offsets)
+
+    def prefill_sequences(self, prompts, slots: Sequence[int], pos=0) -> BatchResult:
+        """Prompts straight into their KV slots by batch_extend calls of at most LLMI_BATCH_TOKENS_MAX token rows
+        (plan_extend_calls: long prompts cut into consecutive spans across calls, short ones packed several per
+        call).  Returns each prompt's last greedy id and log-sum-exp (.argmax / .lse, one entry per prompt)."""
+        prompts = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in prompts]
+        am, lse = np.zeros(len(prompts), np.int32), np.zeros(len(prompts), np.float32)
+        for call in plan_extend_calls([x.size for x in prompts], slots, pos, BATCH_TOKENS_MAX):
+            r = self.batch_extend([prompts[sp.prompt][sp.start:sp.start + sp.n_tokens] for sp in call],
+                                  [sp.slot for sp in call], [sp.pos for sp in call], [sp.out for sp in call])
+            for i, sp in enumerate(call):
+                if sp.out == "last":
+                    am[sp.prompt], lse[sp.prompt] = r.argmax[r.offsets[i]], r.lse[r.offsets[i]]
+        return BatchResult(am, lse, None)
 
     def batch_generate(self, first: Sequence[int], slots: Sequence[int], pos: Sequence[int], n_steps: int,
                        stop: Sequence[int] = (), samplers=None) -> np.ndarray:
