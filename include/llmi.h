@@ -312,6 +312,58 @@ int llmi_session_batch_generate_sampled(llmi_session* s, const int32_t* first, c
                                         int B, int n_steps, const int32_t* stop, int n_stop,
                                         const llmi_sampler* samplers, int32_t* out);
 
+/* Lookup decoding: llmi_session_batch_generate's greedy loop with n-gram drafts verified inside
+ * the device loop.  Every step runs, per row, the span [current token, up to draft_len draft tokens] -- one ragged
+ * step of llmi_session_batch_extend's kind over B (draft_len + 1) token rows -- and one launch accepts the drafts that
+ * were the greedy ids, appends the emitted ids to the row's history and drafts the next step; tokens, positions,
+ * histories and ids stay on the device.
+ * The rule (pure integer).  A row's history h[0..L), ngram_max = N, ngram_min, draft_len = D:
+ *   - for every candidate end e in [0, L-2], ml(e) = the largest k <= min(N, e+1, L-1) with h[e-k+1..e] == h[L-k..L-1];
+ *   - among the candidates with ml(e) >= ngram_min the largest (ml(e), e) wins: the longer n-gram first, then the most
+ *     recent occurrence; none: the draft is empty;
+ *   - else c = e+1, P = L-c and d[j] = h[c + (j mod P)] for j = 0..nd-1 (a continuation that reaches the end of the
+ *     history wraps periodically, so a repeating tail drafts its full length);
+ *   - nd = min(D, remaining-1), `remaining` what is left of the row's max_new: no draft is ever written at or past
+ *     pos + max_new.
+ * Accept.  The span [cur, d[0..nd)] ran at positions p..p+nd, a[j] = the arg-max of span row j: emit a[0]; for
+ * j = 1..nd emit a[j] if d[j-1] == a[j-1], else stop; truncate after the first stop id, inclusive (that ends the row);
+ * truncate to `remaining`.  With m ids emitted: they are appended to the history, cur = the last one, pos += m; the row
+ * is done when `remaining` reaches 0 or a stop id was emitted.
+ * hist: the rows' histories concatenated (hist_len[b] tokens each).  Row b's last history token is the token to run at
+ * pos[b] (llmi_session_batch_generate's first[b]); the history need not be the slot's real token list -- it only
+ * steers the drafts.  Steps are enqueued in groups of LLMI_LOOKUP_SYNC (environment, default 4, read at the call); after
+ * each group the B done flags are read back in one copy, and the call returns when every row is done or max_steps
+ * steps have run (0: max_new).  out[b][0..n_out[b]) = row b's ids, -1 past them.
+ * Contract (no tolerance): under the row contract above on the slots' K/V, out[b] equals row b's ids of
+ * llmi_session_batch_generate(first = the row's last history token, slots, pos, n_steps = max_new, stop) on the same
+ * state, up to and including the row's stop id -- whatever the histories, draft_len, the n-gram bounds, B, the other
+ * rows, the row order and LLMI_LOOKUP_SYNC -- because every span row carries llmi_session_score's bits.  K/V rows
+ * pos[b] .. pos[b]+n_out[b]-1 left in the slot are the bits llmi_session_batch_generate leaves there; rows from
+ * pos[b]+n_out[b] up to pos[b]+max_new-1 may hold rejected drafts; rows at and past pos[b]+max_new are never touched.
+ * The one condition is the GEMM switch of llmi_session_batch_extend's contract: the step's B (draft_len + 1) token
+ * rows must stay on the side of the switch that llmi_session_batch_generate's B rows are on (at most 384 rows on the
+ * 4B shapes, 128 on the 27B shapes, any on the 1B: DESIGN.md section 14.1).  f16 overflow: as
+ * llmi_session_batch_generate, the loop does not leave the device and does not check.
+ * stats (may be NULL) is a pure function of the emitted ids, the histories and the parameters: steps = the steps in
+ * which some row was live, drafted[b] = the draft tokens row b ran, accepted[b] = the ids it emitted past the first of
+ * each step.
+ * Checks (each message names the argument): sessions as llmi_session_seq_reserve; B, the slots and n_stop as
+ * llmi_session_batch_generate; 1 <= draft_len <= 31; 1 <= ngram_min <= ngram_max <= 8; max_new >= 1;
+ * B (draft_len + 1) <= LLMI_BATCH_TOKENS_MAX; hist_len >= 1; token ids in range; pos >= 1 (LLMI_E_RANGE: a position-0
+ * row is a one-token prompt, which runs as a decode step of its own -- llmi_session_batch_generate runs it before its
+ * loop, a lookup step would need it inside); pos + max_new <= max_ctx; max_steps >= 0. */
+typedef struct { int32_t draft_len, ngram_max, ngram_min, max_new; } llmi_lookup;           /* 16 bytes */
+typedef struct { int32_t steps; int32_t drafted[LLMI_SEQ_MAX]; int32_t accepted[LLMI_SEQ_MAX]; } llmi_lookup_stats;
+int llmi_session_batch_generate_lookup(llmi_session* s, const int32_t* hist, const int32_t* hist_len,
+                                       const int32_t* slots, const int32_t* pos, int B, const llmi_lookup* lk,
+                                       int max_steps, const int32_t* stop, int n_stop, int32_t* out, int32_t* n_out,
+                                       llmi_lookup_stats* stats);
+/* op level, host pointers, synchronous: the draft rule alone, by the same kernel.  draft: draft_len entries;
+ * *n_draft = the tokens drafted (0: no match; else draft_len), *match_end = e (-1: none), *match_len = ml(e)
+ * (each may be NULL).  L >= 1, 1 <= draft_len <= 31, 1 <= ngram_min <= ngram_max <= 8. */
+int llmi_lookup_draft(const int32_t* hist, int L, int ngram_max, int ngram_min, int draft_len, int32_t* draft,
+                      int* n_draft, int* match_end, int* match_len);
+
 /* op level, host pointers, synchronous: the multi-row F16 logits GEMV alone.  x16: [T][E] f16 bits, w16: [V][E] f16
  * bits (row-major), logits: [T][V], softcap <= 0: none.  logits[t] carries the bits of the fast F16
  * llmi_mat_vec_mul of w16 with row t.  E % 128 == 0 and E <= 6144, else LLMI_E_SIZE.  llmi_logits_rows_rb: the rows
@@ -404,7 +456,11 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *  12 = the span attention launch (+ its merge) of the most recent llmi_session_batch_extend step, one pass over
  *       the layers (with LLMI_BATCH_SPAN_ROWS=1 in the environment at that call: the per-token form the step ran);
  *       bytes = the K and V rows 0..last position of every query block of that step, counted once per block, of one
- *       layer (0 / 0 before any such step).
+ *       layer (0 / 0 before any such step);
+ *  13 = lookup_step_kernel's draft search (+ the step's tables) over the rows of the most recent
+ *       llmi_session_batch_generate_lookup call, with that call's parameters, every row searched whatever is left of
+ *       its budget, no state changed; bytes = the history tokens read, 4 bytes x the sum of the rows' history lengths
+ *       as the call left them (0 / 0 before any lookup step).
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

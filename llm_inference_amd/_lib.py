@@ -79,6 +79,19 @@ class Span(C.Structure):
     _fields_ = [("slot", C.c_int32), ("pos", C.c_int32), ("n_tokens", C.c_int32), ("out", C.c_int32)]
 
 
+class Lookup(C.Structure):
+    """llmi_lookup: the lookup loop's parameters (16 bytes)."""
+    _fields_ = [("draft_len", C.c_int32), ("ngram_max", C.c_int32), ("ngram_min", C.c_int32), ("max_new", C.c_int32)]
+
+
+class LookupStats(C.Structure):
+    """llmi_lookup_stats: steps in which some row was live; per row the draft tokens run and the ids emitted past the
+    first of each step."""
+    _fields_ = [("steps", C.c_int32), ("drafted", C.c_int32 * SEQ_MAX), ("accepted", C.c_int32 * SEQ_MAX)]
+
+
+LOOKUP_DRAFT_MAX, LOOKUP_NGRAM_MAX = 31, 8
+
 _lib = None
 _vp, _sz, _u32, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_float, C.c_double
 
@@ -118,6 +131,10 @@ _SIGS = {
     "llmi_session_batch_generate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "llmi_session_batch_generate_sampled": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int,
                                                       C.POINTER(Sampler), _vp]),
+    "llmi_session_batch_generate_lookup": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(Lookup), C.c_int, _vp,
+                                                     C.c_int, _vp, _vp, C.POINTER(LookupStats)]),
+    "llmi_lookup_draft": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "llmi_logits_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp]),
     "llmi_logits_rows_rb": (C.c_int, [C.c_int]),
     "llmi_score_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libllmi.so")
-SOURCES = ["k_gemv.hip", "k_layer.hip", "k_elem.hip", "k_attn.hip", "k_session.hip", "k_prefill.hip", "k_logits.hip", "k_exchange.hip", "k_exact.hip", "k_sample.hip", "k_score.hip", "session.cpp", "session_batch.cpp", "collective.cpp", "capi.cpp"]
+SOURCES = ["k_gemv.hip", "k_layer.hip", "k_elem.hip", "k_attn.hip", "k_session.hip", "k_prefill.hip", "k_logits.hip", "k_exchange.hip", "k_exact.hip", "k_sample.hip", "k_score.hip", "k_lookup.hip", "session.cpp", "session_batch.cpp", "collective.cpp", "capi.cpp"]
 HEADERS = ["common.h", "kernels.h", "attn.h", "layer_body.h", "session_kernels.h", "session.h", "gguf_reader.h", "collective.h",
            "exact.h", "px.h", "glibc_math.h", "spec_chain.h", "sample.h", "score_plan.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -491,6 +491,71 @@ int llmi_session_batch_generate_sampled(llmi_session* s, const int32_t* first, c
   });
 }
 
+int llmi_session_batch_generate_lookup(llmi_session* s, const int32_t* hist, const int32_t* hist_len,
+                                       const int32_t* slots, const int32_t* pos, int B, const llmi_lookup* lk,
+                                       int max_steps, const int32_t* stop, int n_stop, int32_t* out, int32_t* n_out,
+                                       llmi_lookup_stats* stats) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer");
+    if (!hist) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (hist)");
+    if (!hist_len) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (hist_len)");
+    if (!slots) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (slots)");
+    if (!pos) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (pos)");
+    if (!lk) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (lk)");
+    if (!out) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (out)");
+    if (!n_out) throw status_error(LLMI_E_ARG, "batch_generate_lookup: null pointer (n_out)");
+    s->s->batch_generate_lookup(hist, hist_len, slots, pos, B, *lk, max_steps, stop, n_stop, out, n_out, stats);
+  });
+}
+
+int llmi_lookup_draft(const int32_t* hist, int L, int ngram_max, int ngram_min, int draft_len, int32_t* draft,
+                      int* n_draft, int* match_end, int* match_len) {
+  return guard([&] {
+    if (!hist) throw status_error(LLMI_E_ARG, "lookup_draft: null pointer (hist)");
+    if (!draft) throw status_error(LLMI_E_ARG, "lookup_draft: null pointer (draft)");
+    if (L < 1) throw status_error(LLMI_E_RANGE, "lookup_draft: a history needs at least one token (L)");
+    if (draft_len < 1 || draft_len > LOOKUP_DRAFT_MAX)
+      throw status_error(LLMI_E_RANGE, "lookup_draft: draft_len must be in 1..31 (draft_len)");
+    if (ngram_max < 1 || ngram_max > LOOKUP_NGRAM_MAX)
+      throw status_error(LLMI_E_RANGE, "lookup_draft: ngram_max must be in 1..8 (ngram_max)");
+    if (ngram_min < 1 || ngram_min > ngram_max)
+      throw status_error(LLMI_E_RANGE, "lookup_draft: ngram_min must be in 1..ngram_max (ngram_min)");
+    Ctx& c = ctx();
+    const int W = draft_len + 1;
+    int32_t* hd = (int32_t*)c.get(0, (size_t)L * 4);
+    // slot 1: the row's state, then the step's tables of one row -- token ids, token rows, the block, the done flag
+    uint8_t* misc = (uint8_t*)c.get(1, 256 + (size_t)W * 16);
+    LookupRow r{};
+    r.hist = hd;
+    r.len = r.cap = L;
+    r.remaining = W;  // nd = min(draft_len, remaining - 1) = draft_len
+    r.match_end = -1;
+    LookupArgs a;
+    a.rows = (LookupRow*)misc;
+    a.B = 1;
+    a.D = draft_len;
+    a.ngram_max = ngram_max;
+    a.ngram_min = ngram_min;
+    a.mode = LOOKUP_DRAFT;
+    a.blocks = (AttnBlock*)(misc + 64);
+    a.done = (int32_t*)(misc + 128);
+    a.tok = (int32_t*)(misc + 256);
+    a.trows = (SeqRow*)(misc + 256 + (size_t)W * 4);
+    a.max_new = W;
+    LLMI_HIP(hipMemcpyAsync(hd, hist, (size_t)L * 4, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(a.rows, &r, sizeof(r), hipMemcpyHostToDevice, c.stream));
+    launch_lookup_step(a, c.stream);
+    std::vector<int32_t> tok((size_t)W);
+    LLMI_HIP(hipMemcpyAsync(&r, a.rows, sizeof(r), hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipMemcpyAsync(tok.data(), a.tok, (size_t)W * 4, hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipStreamSynchronize(c.stream));
+    for (int j = 0; j < draft_len; j++) draft[j] = j < r.nd ? tok[(size_t)j + 1] : -1;
+    if (n_draft) *n_draft = r.nd;
+    if (match_end) *match_end = r.match_end;
+    if (match_len) *match_len = r.match_len;
+  });
+}
+
 int llmi_logits_rows_rb(int E) { return logits_rows_rb(E); }
 
 int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits) {

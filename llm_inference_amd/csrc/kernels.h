@@ -116,4 +116,42 @@ void launch_score_rows(const ScoreArgs& a, hipStream_t s);
 void launch_score_reduce_row(const float* logits, int V, int target, float* logprob, float* lse, int32_t* argmax,
                              hipStream_t s);
 
+// ---- lookup decoding (k_lookup.hip) ----
+struct SeqRow;     // (session_kernels.h)
+struct AttnBlock;
+constexpr int LOOKUP_NGRAM_MAX = 8, LOOKUP_DRAFT_MAX = 31;
+// A row's state, device-resident across the steps of one call.  hist[len - 1] is the token the next step runs at
+// `pos` of KV slot `slot`; cap >= the initial len + max_new.
+struct LookupRow {
+  int32_t* hist;
+  int32_t len, cap, slot, pos;
+  int32_t remaining, n_out, done;  // of max_new; ids emitted so far; 1: a stop id was emitted or remaining == 0
+  int32_t nd;                      // draft tokens of the step being run (token rows 1..nd of the row's span)
+  int32_t steps, drafted, accepted;  // steps the row was live in; sum of nd; ids emitted past each step's first
+  int32_t match_end, match_len;      // the last draft's match (e, ml(e)); -1 / 0: none
+  int32_t pad;
+};
+enum { LOOKUP_STEP = 0, LOOKUP_DRAFT = 1, LOOKUP_TIME = 2 };
+// One work-group per row b, its token rows b (D + 1) .. of the step's tables.
+// LOOKUP_STEP: accept the step just scored (argmax: the scorer's ids of all B (D + 1) rows; emit a[0], then a[j] while
+// d[j-1] == a[j-1]; cut after a stop id; never past `remaining`), append to hist and out[b][n_out..], then draft and
+// write the next step's tables.  LOOKUP_DRAFT: the draft and the tables only (the first step; the op-level call).
+// LOOKUP_TIME: the draft search of every row whatever its budget, tables written, no state changed (time_kernel(13)).
+// Tables: tok [B (D + 1)] (row 0 the current token, 1..nd the draft, the rest a valid id), trows {slot, pos + j} for
+// j <= nd else pos -1, blocks[b] = {b (D + 1), 1 + nd, slot, pos}; a finished row: every pos -1.  done: [B] flags.
+struct LookupArgs {
+  LookupRow* rows = nullptr;
+  int B = 0, D = 0, ngram_max = 0, ngram_min = 0, mode = LOOKUP_STEP;
+  const int32_t* argmax = nullptr;
+  int32_t* tok = nullptr;
+  SeqRow* trows = nullptr;
+  AttnBlock* blocks = nullptr;
+  int32_t* out = nullptr;  // [B][max_new]
+  int max_new = 0;
+  int32_t* done = nullptr;
+  int32_t stop[4] = {0, 0, 0, 0};
+  int n_stop = 0;
+};
+void launch_lookup_step(const LookupArgs& a, hipStream_t s);
+
 }  // namespace llmi

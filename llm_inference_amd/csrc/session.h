@@ -94,6 +94,10 @@ class Session {
   // ragged batch steps: spans of consecutive tokens, each on its own slot
   void batch_extend(const int32_t* tokens, const llmi_span* spans, int n_spans, float* logits, int32_t* argmax,
                     float* lse);
+  // lookup decoding: n-gram drafts verified inside the device loop
+  void batch_generate_lookup(const int32_t* hist, const int32_t* hist_len, const int32_t* slots, const int32_t* pos,
+                             int B, const llmi_lookup& lk, int max_steps, const int32_t* stop, int n_stop, int32_t* out,
+                             int32_t* n_out, llmi_lookup_stats* stats);
   // per-row seeded sampling inside the batch loop; samplers: B entries
   void batch_generate_sampled(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                               const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);
@@ -372,6 +376,24 @@ class Session {
   // holds that many rows' partials) one per LLMI_SEQ_MAX rows
   void launch_batch_attn(const PrefillAttn& at, int T, hipStream_t s);
   void time_extend_attn(int reps, double* us, double* bytes);
+  void ensure_extend_buffers();  // bx_* and bt_apart_
+  // lookup decoding (llmi_session_batch_generate_lookup): the step's tables live on the device
+  // and are written by lookup_step_kernel; grow-only buffers
+  LookupRow* lk_rowst_ = nullptr;    // [LLMI_SEQ_MAX] the rows' state
+  int32_t* lk_hist_ = nullptr;       // the rows' history buffers, back to back (hist_len + max_new each)
+  size_t lk_hist_cap_ = 0;
+  int32_t* lk_out_ = nullptr;        // [B][max_new] the output ring
+  size_t lk_out_cap_ = 0;
+  int32_t* lk_done_ = nullptr;       // [LLMI_SEQ_MAX] done flags, read back once per group of steps
+  int32_t* lk_tok_ = nullptr;        // [LLMI_BATCH_TOKENS_MAX] the step's token ids ...
+  SeqRow* lk_trows_ = nullptr;       // ... its token rows
+  AttnBlock* lk_blocks_ = nullptr;   // [LLMI_SEQ_MAX] ... and its query blocks, one per row
+  int32_t* lk_ttok_ = nullptr;       // time_kernel(13)'s tables
+  SeqRow* lk_ttrows_ = nullptr;
+  AttnBlock* lk_tblocks_ = nullptr;
+  LookupArgs lk_last_{};             // the most recent lookup step's launch (B = 0: none yet)
+  double lk_last_bytes_ = 0.0;       // 4 x the rows' history lengths after that call
+  void time_lookup_step(int reps, double* us, double* bytes);
 };
 
 }  // namespace llmi

@@ -3,7 +3,8 @@
 // position of its own KV slot, then the scorer's rows; the greedy loop adds one feedback launch per step, the
 // sampled loop (section 13) the rows' full logits and the sampler's two multi-row launches.  A ragged step
 // (llmi_session_batch_extend, section 14) carries spans of consecutive tokens: prompt chunks and draft tokens beside
-// decode rows, the attention in its span form.
+// decode rows, the attention in its span form.  The lookup loop (llmi_session_batch_generate_lookup, section 15) runs
+// such steps with the tables written on the device: n-gram drafts verified and accepted without leaving it.
 #include "session.h"
 
 #include <algorithm>
@@ -251,6 +252,25 @@ void Session::launch_batch_attn(const PrefillAttn& at, int T, hipStream_t s) {
   }
 }
 
+void Session::ensure_extend_buffers() {
+  const int E = hp_.n_embd;
+  if (!bx_rows_) {
+    int maxhd = 0;
+    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
+    const size_t max_blocks = LLMI_SEQ_MAX + LLMI_BATCH_TOKENS_MAX / 32;
+    bx_rows_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
+    bx_tok_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
+    bx_blocks_ = dalloc<AttnBlock>(max_blocks);
+    bx_apart_ = dalloc<float>((size_t)nh_ * max_blocks * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
+    bx_x16_ = dalloc<uint16_t>((size_t)LLMI_BATCH_TOKENS_MAX * E);
+  }
+  if (!bt_apart_) {  // (the per-token form's partials, as batch_step)
+    int maxhd = 0;
+    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
+    bt_apart_ = dalloc<float>((size_t)nh_ * LLMI_SEQ_MAX * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
+  }
+}
+
 // A ragged batch step: the batched prefill's launch sequence over the spans' token rows -- the
 // q/k launch with one SeqRow per token row, the attention in its span form (one query block per 32 consecutive
 // tokens of a span) -- then the final norm, the scorer and the logits GEMV over the output rows only.
@@ -286,21 +306,7 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
   ensure_usable();
   hipStream_t s = stream_;
   const int E = hp_.n_embd;
-  if (!bx_rows_) {
-    int maxhd = 0;
-    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
-    const size_t max_blocks = LLMI_SEQ_MAX + LLMI_BATCH_TOKENS_MAX / 32;
-    bx_rows_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
-    bx_tok_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
-    bx_blocks_ = dalloc<AttnBlock>(max_blocks);
-    bx_apart_ = dalloc<float>((size_t)nh_ * max_blocks * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
-    bx_x16_ = dalloc<uint16_t>((size_t)LLMI_BATCH_TOKENS_MAX * E);
-  }
-  if (!bt_apart_) {  // (the per-token form's partials, as batch_step)
-    int maxhd = 0;
-    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
-    bt_apart_ = dalloc<float>((size_t)nh_ * LLMI_SEQ_MAX * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
-  }
+  ensure_extend_buffers();
   // A/B, read at the call: the step's attention through the per-token multi-sequence form, one SeqRow per token row
   // (legal because the q/k launch has appended the step's K/V before it; the same bits)
   const char* sr_env = getenv("LLMI_BATCH_SPAN_ROWS");
@@ -558,6 +564,216 @@ void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* sl
     bt_samp_rows_ = rows;
   }
   check_device_error();
+}
+
+// Lookup decoding.  A step is batch_extend's launch sequence over B spans of draft_len + 1 token
+// rows -- prefill_layers with the span attention, the final norm and the scorer over every row -- whose tables
+// lookup_step_kernel writes on the device; the same launch accepts the step just scored.  Steps are enqueued in groups
+// and only the B done flags come back between groups.  f16 overflow: as batch_generate, the loop does not leave the
+// device and does not check.
+void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len, const int32_t* slots,
+                                    const int32_t* pos, int B, const llmi_lookup& lk, int max_steps, const int32_t* stop,
+                                    int n_stop, int32_t* out, int32_t* n_out, llmi_lookup_stats* stats) {
+  const std::string f = "batch_generate_lookup: ";
+  if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
+  if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
+  if (B < 1 || B > n_seq_) throw status_error(LLMI_E_RANGE, f + "B must be in 1..n_seq (B)");
+  if (n_stop < 0 || n_stop > 4) throw status_error(LLMI_E_ARG, f + "at most 4 stop ids (n_stop)");
+  if (n_stop > 0 && !stop) throw status_error(LLMI_E_ARG, f + "null pointer (stop)");
+  if (lk.draft_len < 1 || lk.draft_len > LOOKUP_DRAFT_MAX)
+    throw status_error(LLMI_E_RANGE, f + "draft_len must be in 1..31 (draft_len)");
+  if (lk.ngram_max < 1 || lk.ngram_max > LOOKUP_NGRAM_MAX)
+    throw status_error(LLMI_E_RANGE, f + "ngram_max must be in 1..8 (ngram_max)");
+  if (lk.ngram_min < 1 || lk.ngram_min > lk.ngram_max)
+    throw status_error(LLMI_E_RANGE, f + "ngram_min must be in 1..ngram_max (ngram_min)");
+  if (lk.max_new < 1) throw status_error(LLMI_E_RANGE, f + "max_new must be at least 1 (max_new)");
+  if (B * (lk.draft_len + 1) > LLMI_BATCH_TOKENS_MAX)
+    throw status_error(LLMI_E_RANGE, f + "more than " + std::to_string(LLMI_BATCH_TOKENS_MAX) +
+                                         " token rows in one step (B * (draft_len + 1))");
+  if (max_steps < 0) throw status_error(LLMI_E_ARG, f + "negative step count (max_steps)");
+  LookupArgs a;
+  a.n_stop = n_stop;
+  for (int i = 0; i < n_stop; i++) {
+    if (stop[i] < 0 || stop[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "stop id out of range (stop)");
+    a.stop[i] = stop[i];
+  }
+  const int D = lk.draft_len, W = D + 1, T = B * W, max_new = lk.max_new, E = hp_.n_embd;
+  bool seen[LLMI_SEQ_MAX] = {};
+  size_t n_hist = 0, hist_cap = 0;
+  int p0 = 0;
+  for (int b = 0; b < B; b++) {
+    if (slots[b] < 0 || slots[b] >= n_seq_) throw status_error(LLMI_E_RANGE, f + "slot outside [0, n_seq) (slots)");
+    if (seen[slots[b]]) throw status_error(LLMI_E_ARG, f + "duplicate slot in one call (slots)");
+    seen[slots[b]] = true;
+    if (hist_len[b] < 1) throw status_error(LLMI_E_RANGE, f + "a history needs at least one token (hist_len)");
+    // a position-0 row is a one-token prompt, which forward / score run as a decode step (batch_row0): batch_generate
+    // runs it before its loop, a lookup step would need it inside
+    if (pos[b] < 1)
+      throw status_error(LLMI_E_RANGE, f + "a row must start at position 1 or later: position 0 is a one-token prompt, "
+                                           "which runs as a decode step the lookup loop does not have (pos)");
+    if (pos[b] > max_ctx_ - max_new) throw status_error(LLMI_E_RANGE, f + "context overflow (pos + max_new)");
+    n_hist += (size_t)hist_len[b];
+    hist_cap += (size_t)hist_len[b] + (size_t)max_new;
+    p0 = std::max(p0, pos[b] + max_new - 1);
+  }
+  for (size_t i = 0; i < n_hist; i++)
+    if (hist[i] < 0 || hist[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "token id out of range (hist)");
+  ensure_usable();
+  int group = 4;
+  if (const char* c = getenv("LLMI_LOOKUP_SYNC")) group = std::max(1, atoi(c));
+  const int cap_steps = max_steps == 0 ? max_new : max_steps;
+  hipStream_t s = stream_;
+  ensure_extend_buffers();
+  if (!lk_rowst_) {
+    lk_rowst_ = dalloc<LookupRow>(LLMI_SEQ_MAX);
+    lk_done_ = dalloc<int32_t>(LLMI_SEQ_MAX);
+    lk_tok_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
+    lk_trows_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
+    lk_blocks_ = dalloc<AttnBlock>(LLMI_SEQ_MAX);
+    lk_ttok_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
+    lk_ttrows_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
+    lk_tblocks_ = dalloc<AttnBlock>(LLMI_SEQ_MAX);
+  }
+  if (hist_cap > lk_hist_cap_) {  // grow-only, as the prefill's chunk buffers
+    lk_hist_cap_ = std::max(hist_cap, 2 * lk_hist_cap_);
+    lk_hist_ = dalloc<int32_t>(lk_hist_cap_);
+  }
+  if ((size_t)B * max_new > lk_out_cap_) {
+    lk_out_cap_ = std::max((size_t)B * max_new, 2 * lk_out_cap_);
+    lk_out_ = dalloc<int32_t>(lk_out_cap_);
+  }
+  lk_last_.B = 0;  // (until this call has run a step: time_kernel(13) reads the buffers above)
+  // the histories once, each into its own buffer of hist_len + max_new tokens, and the rows' state
+  std::vector<int32_t> hbuf(hist_cap, 0);
+  std::vector<LookupRow> st((size_t)B);
+  size_t src = 0, dst = 0;
+  for (int b = 0; b < B; b++) {
+    std::memcpy(hbuf.data() + dst, hist + src, (size_t)hist_len[b] * 4);
+    LookupRow r{};
+    r.hist = lk_hist_ + dst;
+    r.len = hist_len[b];
+    r.cap = hist_len[b] + max_new;
+    r.slot = slots[b];
+    r.pos = pos[b];
+    r.remaining = max_new;
+    r.match_end = -1;
+    st[(size_t)b] = r;
+    src += (size_t)hist_len[b];
+    dst += (size_t)r.cap;
+  }
+  h2d(lk_hist_, hbuf.data(), hist_cap * 4);
+  h2d(lk_rowst_, st.data(), (size_t)B * sizeof(LookupRow));
+  LLMI_HIP(hipMemsetAsync(lk_out_, 0xFF, (size_t)B * max_new * 4, s));  // -1 past n_out
+  ensure_prefill_buffers(T);
+  ensure_score_buffers(std::max(T, pf_cap_));
+  a.rows = lk_rowst_;
+  a.B = B;
+  a.D = D;
+  a.ngram_max = lk.ngram_max;
+  a.ngram_min = lk.ngram_min;
+  a.argmax = sc_amax_;
+  a.tok = lk_tok_;
+  a.trows = lk_trows_;
+  a.blocks = lk_blocks_;
+  a.out = lk_out_;
+  a.max_new = max_new;
+  a.done = lk_done_;
+  a.mode = LOOKUP_DRAFT;  // the first step's draft and tables
+  launch_lookup_step(a, s);
+  a.mode = LOOKUP_STEP;
+  ScoreArgs sa;
+  sa.x16 = sc_x16_;
+  sa.xstride = E;
+  sa.w16 = static_cast<const uint16_t*>(logits_w_.qs);
+  sa.T = T;
+  sa.V = vocab_;
+  sa.E = E;
+  sa.softcap = hp_.final_softcap;
+  sa.targets = nullptr;
+  sa.ms = sc_ms_;
+  sa.key = sc_key_;
+  sa.tl = sc_tl_;
+  sa.logprob = sc_lp_;
+  sa.lse = sc_lse_;
+  sa.argmax = sc_amax_;
+  const bool f16_all = prefill_f16_ok();
+  // the span attention's launches are recorded for time_kernel(12), which times batch_extend's steps: kept as they were
+  const std::vector<PrefillAttn> keep_attn = bx_last_attn_;
+  std::vector<int32_t> flags((size_t)B, 0);
+  bx_step_ = true;
+  try {
+    bool all_done = false;
+    for (int n_run = 0; n_run < cap_steps && !all_done;) {
+      const int g = std::min(group, cap_steps - n_run);
+      for (int i = 0; i < g; i++) {
+        // p0: the last position any row may reach, a bound for the attention's merge launch (as batch_loop's)
+        prefill_layers(lk_tok_, T, p0, /*trim=*/false, /*last_chunk=*/false, f16_all, lk_trows_, lk_blocks_, B);
+        launch_residual_norm_rows16(pf_out_, E, L_.back().post_ffw_norm, pf_resid_, E, out_norm_, sc_x16_, E, E, T,
+                                    hp_.eps, s);
+        launch_score_rows(sa, s);
+        launch_lookup_step(a, s);
+      }
+      n_run += g;
+      LLMI_HIP(hipMemcpyAsync(flags.data(), lk_done_, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+      LLMI_HIP(hipStreamSynchronize(s));
+      all_done = true;
+      for (int b = 0; b < B; b++) all_done = all_done && flags[(size_t)b] != 0;
+    }
+  } catch (...) {
+    bx_step_ = false;
+    bx_last_attn_ = keep_attn;
+    throw;
+  }
+  bx_step_ = false;
+  bx_last_attn_ = keep_attn;
+  sc_last_T_ = T;
+  LLMI_HIP(hipMemcpyAsync(st.data(), lk_rowst_, (size_t)B * sizeof(LookupRow), hipMemcpyDeviceToHost, s));
+  LLMI_HIP(hipMemcpyAsync(out, lk_out_, (size_t)B * max_new * 4, hipMemcpyDeviceToHost, s));
+  LLMI_HIP(hipStreamSynchronize(s));
+  check_device_error();
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  double by = 0.0;
+  for (int b = 0; b < B; b++) {
+    const LookupRow& r = st[(size_t)b];
+    n_out[b] = r.n_out;
+    by += 4.0 * r.len;
+    if (stats) {
+      stats->steps = std::max(stats->steps, r.steps);
+      stats->drafted[b] = r.drafted;
+      stats->accepted[b] = r.accepted;
+    }
+  }
+  lk_last_ = a;
+  lk_last_.mode = LOOKUP_TIME;
+  lk_last_.tok = lk_ttok_;
+  lk_last_.trows = lk_ttrows_;
+  lk_last_.blocks = lk_tblocks_;
+  lk_last_bytes_ = by;
+}
+
+// time_kernel(13): lookup_step_kernel's draft search over the most recent lookup call's rows, into tables of its own
+void Session::time_lookup_step(int reps, double* us, double* bytes) {
+  *us = *bytes = 0.0;
+  if (lk_last_.B == 0 || reps <= 0) return;
+  hipStream_t s = stream_;
+  std::vector<hipEvent_t> ev(2 * (size_t)reps);
+  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+  LLMI_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < reps; r++) {
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+    launch_lookup_step(lk_last_, s);
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
+  }
+  LLMI_HIP(hipStreamSynchronize(s));
+  double tot = 0;
+  for (int r = 0; r < reps; r++) {
+    float ms = 0;
+    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
+    tot += ms;
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  *us = tot * 1000.0 / reps;
+  *bytes = lk_last_bytes_;
 }
 
 // time_kernel(11): the multi-row logits GEMV + select + finalize (no feedback) over the most recent sampled batch

@@ -10,6 +10,7 @@ device session of include/llmi.h.
     ids = m.batch_generate(firsts, slots, positions, n, samplers=dict(temperature=1.0, top_k=64, seed=1))  # sampled
     last = m.prefill_sequences(prompts, slots)            # prompts straight into their slots
     r = m.batch_extend([chunk, [tok], drafts], [0, 1, 2], [128, 40, 64], out=["none", "last", "all"])  # a ragged step
+    r = m.batch_generate_lookup(histories, slots, positions, max_new=64)   # greedy ids, n-gram drafts (section 15)
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 
 from ._lib import (BATCH_TOKENS_MAX, LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, SPAN_ALL,
-                   SPAN_LAST, SPAN_NONE, TP_ID_BYTES, TRACE_FN, Sampler, SessionInfo, SessionOpts, Span, check, lib, ptr)
+                   SPAN_LAST, SPAN_NONE, TP_ID_BYTES, TRACE_FN, Lookup, LookupStats, Sampler, SessionInfo, SessionOpts,
+                   Span, check, lib, ptr)
 from .gguf import GGUFFile
 from .score import ScoreResult, resolve_targets
 
@@ -99,6 +101,28 @@ class ExtendResult:
     lse: np.ndarray               # float32 [n_out]
     logits: Optional[np.ndarray]  # float32 [n_out, vocab] or None
     offsets: np.ndarray           # int64 [n_spans + 1]
+
+
+@dataclass
+class LookupResult:
+    """Model.batch_generate_lookup: per row the ids it emitted (batch_generate's, cut after a stop id); the steps in
+    which some row was live; per row the draft tokens run and the ids emitted past the first of each step."""
+    ids: list                     # B int32 arrays
+    steps: int
+    drafted: np.ndarray           # int32 [B]
+    accepted: np.ndarray          # int32 [B]
+
+
+def marshal_lookup(histories, slots, pos):
+    """Model.batch_generate_lookup's rows as llmi_session_batch_generate_lookup takes them: (the histories
+    concatenated int32, hist_len int32 [B], slots int32 [B], pos int32 [B])."""
+    hs = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in histories]
+    sl, p = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (slots, pos))
+    if not (len(hs) == sl.size == p.size):
+        raise ValueError("histories, slots and pos must have one entry per row")
+    hl = np.array([x.size for x in hs], np.int32)
+    tokens = np.concatenate(hs).astype(np.int32) if hs else np.zeros(0, np.int32)
+    return tokens, hl, sl, p
 
 
 SPAN_OUT = {"last": SPAN_LAST, "all": SPAN_ALL, "none": SPAN_NONE}
@@ -367,6 +391,30 @@ class Model:
         check(lib().llmi_session_batch_generate_sampled(self.h, ptr(t), ptr(sl), ptr(p), t.size, n_steps,
                                                         ptr(st) if st.size else None, st.size, arr, ptr(out)))
         return out[:n_steps]
+
+    def batch_generate_lookup(self, histories, slots: Sequence[int], pos: Sequence[int], max_new: int,
+                              draft_len: int = 7, ngram_max: int = 3, ngram_min: int = 1, stop: Sequence[int] = (),
+                              max_steps: int = 0) -> LookupResult:
+        """llmi_session_batch_generate_lookup: batch_generate's greedy ids with n-gram drafts verified inside the
+        device loop.  histories[b]: row b's token history, whose last token runs at pos[b] of
+        slot slots[b] (batch_generate's first[b]); the rest only steers the drafts.  Every step runs the current token
+        and up to draft_len draft tokens per row -- the continuation of the most recent earlier occurrence of the
+        history's last ngram_max..ngram_min tokens -- and emits one id plus every accepted draft.  ids[b] equals row
+        b's ids of batch_generate(first, slots, pos, max_new, stop), cut after its stop id; max_steps (0: max_new)
+        bounds the steps."""
+        tokens, hl, sl, p = marshal_lookup(histories, slots, pos)
+        st = np.ascontiguousarray(stop, np.int32).reshape(-1)
+        B = hl.size
+        out = np.full((max(B, 1), max(int(max_new), 1)), -1, np.int32)
+        n_out = np.zeros(max(B, 1), np.int32)
+        lk = Lookup(int(draft_len), int(ngram_max), int(ngram_min), int(max_new))
+        stats = LookupStats()
+        check(lib().llmi_session_batch_generate_lookup(self.h, ptr(tokens) if tokens.size else None, ptr(hl), ptr(sl),
+                                                       ptr(p), B, C.byref(lk), int(max_steps),
+                                                       ptr(st) if st.size else None, st.size, ptr(out), ptr(n_out),
+                                                       C.byref(stats)))
+        return LookupResult([out[b, :n_out[b]].copy() for b in range(B)], int(stats.steps),
+                            np.array(stats.drafted[:B], np.int32), np.array(stats.accepted[:B], np.int32))
 
     def enqueue(self, first: int, pos: int, n_steps: int) -> None:
         check(lib().llmi_session_enqueue(self.h, first, pos, n_steps))

@@ -238,6 +238,20 @@ def logits_rows(x16, w16, softcap: float = 0.0) -> np.ndarray:
     return out
 
 
+def lookup_draft(history, ngram_max: int = 3, ngram_min: int = 1, draft_len: int = 7):
+    """llmi_lookup_draft: the lookup loop's draft rule alone, by its kernel.  The draft is the
+    continuation of the most recent earlier occurrence of the history's last n tokens, the longest n in
+    ngram_max..ngram_min first, wrapping periodically at the history's end.  Returns (draft int32 [0 or draft_len],
+    match_end, match_len); no match: (empty, -1, 0)."""
+    import ctypes as C
+    h = np.ascontiguousarray(history, np.int32).reshape(-1)
+    d = np.full(max(int(draft_len), 1), -1, np.int32)
+    n, me, ml = C.c_int(), C.c_int(), C.c_int()
+    check(lib().llmi_lookup_draft(ptr(h) if h.size else None, h.size, int(ngram_max), int(ngram_min), int(draft_len),
+                                  ptr(d), C.byref(n), C.byref(me), C.byref(ml)))
+    return d[:n.value].copy(), me.value, ml.value
+
+
 class DeviceWeight:
     """A GGUF weight uploaded once (llmi_weight_create); multiply many times."""
 
