@@ -63,12 +63,23 @@ def _f16_bits(x: np.ndarray) -> np.ndarray:
 
 
 def fill_random(out: np.ndarray, ttype: int, n_rows: int, n_cols: int, rng: np.random.Generator,
-                scale_lo: float = 0.002, scale_hi: float = 0.02, centered: bool = False) -> None:
+                scale_lo: float = 0.002, scale_hi: float = 0.02, centered: bool = False,
+                scales: str = "positive") -> None:
     """Fill ``out`` (uint8 view of exactly the tensor's bytes) with random blocks.
     centered: Q4_0 nibbles uniform on 1..15 (q - 8 symmetric, zero mean, like
     trained weights) instead of 0..15 (mean -0.5: every projection then adds a
     fixed common-mode direction and a deep random model decodes one token
-    forever)."""
+    forever).
+    scales: the block-scale profile of the quantized types (SCALE_PROFILES,
+    _apply_scale_profile); "positive" is the draw below and nothing else."""
+    if scales not in SCALE_PROFILES:
+        raise ValueError(f"scales={scales!r}: one of {SCALE_PROFILES}")
+    _fill_positive(out, ttype, n_rows, n_cols, rng, scale_lo, scale_hi, centered)
+    if scales != "positive" and ttype in _SCALE_FIELDS:
+        _apply_scale_profile(out, ttype, n_rows, rng, scales, centered)
+
+
+def _fill_positive(out, ttype, n_rows, n_cols, rng, scale_lo, scale_hi, centered) -> None:
     if ttype == TensorType.Q4_0:
         blk = out.reshape(-1, 18)
         if centered:
@@ -130,6 +141,103 @@ def fill_random(out: np.ndarray, ttype: int, n_rows: int, n_cols: int, rng: np.r
         raise ValueError(ttype)
 
 
+# ---------------------------------------------------------------------------
+# block-scale profiles
+# ---------------------------------------------------------------------------
+# "positive": every scale a positive normal f16 within one decade (the draw of _fill_positive).  Real files are not
+# like that: ggml's Q4_0 / Q5_0 quantizers store d = max / -8 and max / -16 of the SIGNED element of largest
+# magnitude (about half the blocks negative), Q6_K's d and int8 sub-scales take both signs, all-zero blocks store
+# d = 0, and the K-quants' d / dmin reach into the f16 subnormals.
+#   "signed"  the positive magnitudes, each scale field's sign drawn at random (Q4_K: d and dmin independently;
+#             with centered=True dmin = 7.5 d keeps d's sign, which is what keeps w = d sc (q - 7.5) zero-mean)
+#   "edge"    "signed", then by block position (j + 3 row) % 8, so that every row of at least 8 blocks holds each:
+#               0  d = +0 or -0, random quants
+#               1  d an f16 subnormal (bits 0x0001..0x03FF), either sign
+#               2  quant extreme A   Q4_0 nibbles 0 | Q5_0 nibbles 0, qh 0 | Q8_0 all -128 | Q4_K scales 0, mins 63
+#                                    | Q6_K sub-scales -128 / 127 alternating
+#               3  quant extreme B   Q4_0 nibbles 15 | Q5_0 nibbles 15, qh all ones | Q8_0 -128 at a quarter of the
+#                                    positions | Q4_K scales 63, mins 0 | Q6_K sub-scales 127 / -128 alternating
+#               4  the smallest normal f16 (0x0400), either sign, on rows that are a multiple of 4
+#               5  Q4_K: dmin = +0 or -0 | Q5_0: qh all zeros (even rows) or all ones (odd rows), random nibbles
+#               6  Q4_K: dmin an f16 subnormal, either sign
+#             where a quant extreme lies outside the positive profile's range (Q8_0 -128, Q6_K |sc| > 64) the
+#             block's |d| is halved, so no |w| exceeds the positive profile's
+#   "wide"    "signed" with |d| = 2^U(-24, 0): log-uniform from the smallest f16 subnormal up to 1.0 (op level only)
+SCALE_PROFILES = ("positive", "signed", "edge", "wide")
+# per type: (block bytes, byte offsets of the f16 scale fields)
+_SCALE_FIELDS = {TensorType.Q4_0: (18, (0,)), TensorType.Q5_0: (22, (0,)), TensorType.Q8_0: (34, (0,)),
+                 TensorType.Q4_K: (144, (0, 2)), TensorType.Q6_K: (210, (208,))}
+
+
+def _apply_scale_profile(out: np.ndarray, ttype: int, n_rows: int, rng: np.random.Generator, profile: str,
+                         centered: bool) -> None:
+    bsz, fields = _SCALE_FIELDS[ttype]
+    blk = out.reshape(-1, bsz)
+    nb = blk.shape[0]
+
+    def get(off):
+        return blk[:, off:off + 2].copy().view(np.uint16).reshape(nb)
+
+    def put(off, bits, where=None):
+        b = np.ascontiguousarray(bits, np.uint16).view(np.uint8).reshape(-1, 2)
+        if where is None:
+            blk[:, off:off + 2] = b
+        else:
+            blk[where, off:off + 2] = b[where]
+
+    def sign():
+        return rng.integers(0, 2, nb).astype(np.uint16) << 15
+
+    if profile == "wide":
+        for off in fields:
+            put(off, _f16_bits(np.exp2(rng.uniform(-24.0, 0.0, nb))) | sign())
+        return
+    s0 = sign()
+    put(fields[0], get(fields[0]) | s0)
+    if ttype == TensorType.Q4_K:
+        put(2, get(2) | (s0 if centered else sign()))
+    if profile == "signed":
+        return
+    bpr = nb // n_rows
+    row, j = np.divmod(np.arange(nb), bpr)
+    cat = (j + 3 * row) % 8
+    d_off = fields[0]
+    put(d_off, sign(), cat == 0)
+    sub = rng.integers(1, 0x400, nb).astype(np.uint16) | sign()
+    put(d_off, sub, cat == 1)
+    if ttype == TensorType.Q4_K:
+        put(2, sign(), cat == 5)
+        put(2, rng.integers(1, 0x400, nb).astype(np.uint16) | sign(), cat == 6)
+    put(d_off, np.uint16(0x0400) | sign(), (cat == 4) & (row % 4 == 0))
+    a, b = cat == 2, cat == 3
+    if ttype == TensorType.Q4_0:
+        blk[a, 2:] = 0x00
+        blk[b, 2:] = 0xFF
+    elif ttype == TensorType.Q5_0:
+        blk[a, 2:] = 0x00
+        blk[b, 2:] = 0xFF
+        c = cat == 5
+        blk[c & (row % 2 == 0), 2:6] = 0x00
+        blk[c & (row % 2 == 1), 2:6] = 0xFF
+    elif ttype == TensorType.Q8_0:
+        blk[a, 2:] = 0x80
+        q = blk[:, 2:]
+        q[b[:, None] & (rng.integers(0, 4, (nb, 32)) == 0)] = 0x80
+    elif ttype == TensorType.Q4_K:
+        # get_scale_min_k4: scales in the low 6 bits of bytes 0..3 (j < 4) and the low nibble of 8..11 plus the top
+        # two bits of 0..3; mins in the low 6 bits of 4..7 and the high nibble of 8..11 plus the top two bits of 4..7
+        blk[a, 4:8], blk[a, 8:12], blk[a, 12:16] = 0x00, 0xFF, 0xF0   # scales 0, mins 63
+        blk[b, 4:8], blk[b, 8:12], blk[b, 12:16] = 0xFF, 0x00, 0x0F   # scales 63, mins 0
+    elif ttype == TensorType.Q6_K:
+        alt = np.tile(np.array([-128, 127], np.int8).view(np.uint8), 8)
+        blk[a, 192:208] = alt
+        blk[b, 192:208] = alt[::-1]
+    if ttype in (TensorType.Q8_0, TensorType.Q6_K):
+        d = get(d_off)
+        half = _f16_bits(d.view(np.float16).astype(np.float32) * np.float32(0.5))
+        put(d_off, half | (d & np.uint16(0x8000)), a | b)
+
+
 def random_tensor(ttype: int, n_rows: int, n_cols: int, seed: int = 0, **kw) -> np.ndarray:
     out = np.zeros(row_bytes(ttype, n_cols) * n_rows, dtype=np.uint8)
     fill_random(out, ttype, n_rows, n_cols, np.random.default_rng(seed), **kw)
@@ -142,10 +250,12 @@ def random_tensor(ttype: int, n_rows: int, n_cols: int, seed: int = 0, **kw) -> 
 def build_gemma3_gguf(cfg: Gemma3Config, seed: int = 0, wtype: int = TensorType.Q4_0,
                       embd_type: int = TensorType.F16, wtypes: Optional[Dict[str, int]] = None,
                       swa_pattern: Optional[list] = None, centered: bool = False,
-                      pieces: Optional[list] = None, extra_meta: Optional[Dict[str, object]] = None) -> np.ndarray:
+                      pieces: Optional[list] = None, extra_meta: Optional[Dict[str, object]] = None,
+                      scales: str = "positive") -> np.ndarray:
     """Random-init Gemma-3 GGUF with the tensor names/shapes model.cpp maps
     (model.cpp:169-238).  Returns the whole file as a uint8 numpy array.
-    extra_meta: more metadata keys (without the "gemma3." prefix)."""
+    extra_meta: more metadata keys (without the "gemma3." prefix).
+    scales: the block-scale profile of every quantized tensor (SCALE_PROFILES; "wide" is for single ops)."""
     rng = np.random.default_rng(seed)
     b = GGUFBuilder(align_tensors=True)
     a = "gemma3"
@@ -202,7 +312,7 @@ def build_gemma3_gguf(cfg: Gemma3Config, seed: int = 0, wtype: int = TensorType.
             v.view(np.float32)[:] = rng.uniform(0.6, 1.4, size=v.size // 4).astype(np.float32)
         else:
             n_rows = shape[1] if len(shape) > 1 else 1
-            fill_random(v, tt, n_rows, shape[0], rng, centered=centered)
+            fill_random(v, tt, n_rows, shape[0], rng, centered=centered, scales=scales)
     return buf
 
 

@@ -56,6 +56,68 @@ def gemv_inputs(name, ttype, n_rows, n_cols):
     return w, x
 
 
+# ---- signed / zero / subnormal block scales (synthetic.SCALE_PROFILES) and edge activations: gen_edge.py ----------
+EDGE_PROFILES = ("signed", "edge", "wide")
+EDGE_TYPES = (("q4_0", T.Q4_0), ("q5_0", T.Q5_0), ("q8_0", T.Q8_0), ("q4_k", T.Q4_K), ("q6_k", T.Q6_K))
+# the smallest shapes at which a row kernel can go wrong (one row, fewer rows than a work-group's, more than one
+# work-group; one block, an odd block count) and one real width per type
+_EDGE_REAL = {"q4_0": ((32, 2560), (24, 10240)), "q5_0": ((40, 1152),), "q8_0": ((40, 1152),),
+              "q4_k": ((32, 2560),), "q6_k": ((32, 2560), (24, 10240))}
+
+
+def _edge_shapes(tname):
+    cols = (256, 512) if tname.endswith("_k") else (32, 96)
+    return tuple((r, c) for c in cols for r in (1, 7, 65)) + _EDGE_REAL[tname]
+
+
+# (name, ggml type, n_rows, n_cols, scale profile, activation kind)
+EDGE_GEMV_CASES = [(f"{p}__{tn}_{r}x{c}", tt, r, c, p, "normal")
+                   for tn, tt in EDGE_TYPES for p in EDGE_PROFILES for r, c in _edge_shapes(tn)]
+EDGE_GEMV_CASES += [(f"signed__{tn}_{r}x{c}__{xk}", tt, r, c, "signed", xk)
+                    for tn, tt, (r, c) in (("q4_0", T.Q4_0, (32, 2560)), ("q8_0", T.Q8_0, (40, 1152)),
+                                           ("q4_k", T.Q4_K, (32, 2560)))
+                    for xk in ("edgex", "zerox")]
+EDGE_DEQ_CASES = [(T.Q8_0, 2560), (T.Q5_0, 1152), (T.Q4_K, 2560), (T.Q6_K, 2560)]  # (no Q4_0 dequantize_row exists)
+
+
+def edge_x(n, blk, rng):
+    """N(0, 1) with, per quantization block of ``blk`` elements (32: Q8_0, 256: Q8_K): block 0 all zero (d = 0),
+    block 1 a negative constant, block 2 all 1e-30 (a scale far below f16), block 3 one 3e4 outlier; for blk = 256
+    also a zero and a constant 32-element sub-block (bsums) inside block 4."""
+    x = rng.standard_normal(n).astype(np.float32)
+    x[0:blk] = 0.0
+    x[blk:2 * blk] = -3.0
+    x[2 * blk:3 * blk] = 1e-30
+    x[3 * blk + 5] = 3e4
+    if blk == 256:
+        x[4 * blk + 32:4 * blk + 64] = 0.0
+        x[4 * blk + 96:4 * blk + 128] = -3.0
+    return x
+
+
+def edge_gemv_inputs(name, ttype, n_rows, n_cols, profile, xkind, salt=0):
+    """salt: the try gen_edge.py settled on (stored beside the outputs as ``__salt``)."""
+    seed = int(hashlib.sha256(f"{name}/{salt}".encode()).hexdigest()[:8], 16)
+    w = random_tensor(ttype, n_rows, n_cols, seed=seed, scales=profile)
+    rng = np.random.default_rng(seed + 1)
+    if xkind == "normal":
+        x = rng.standard_normal(n_cols).astype(np.float32)
+    elif xkind == "edgex":
+        x = edge_x(n_cols, 256 if ttype in (T.Q4_K, T.Q6_K) else 32, rng)
+    else:
+        x = np.zeros(n_cols, np.float32)
+    return w, x
+
+
+def edge_deq_input(ttype, n):
+    return random_tensor(ttype, 1, n, seed=4100 + ttype, scales="edge")
+
+
+def fast_gemv_bound(ref):
+    """tests/test_hip_ops.py: fp32 reassociation of the same exact integer block dots."""
+    return 1e-4 * float(np.abs(ref).max()) + 1e-6
+
+
 def quant_input(kind, n, k=0):
     rng = np.random.default_rng(1000 + n + k)
     x = (rng.standard_normal(n) * rng.uniform(0.01, 30.0, size=n // 32).repeat(32)).astype(np.float32)

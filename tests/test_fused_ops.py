@@ -202,6 +202,40 @@ def test_ops_prefill_kquant_gemm(oracle, monkeypatch):
     assert "prefill_gemm16_qkv" in chk.report and "prefill_gemm16_down" in chk.report
 
 
+def _edge_cases():
+    from llm_inference_amd.gguf import TensorType as TT
+    kq = dict(wtype=TT.Q4_K, wtypes={"v": TT.Q6_K, "down": TT.Q6_K}, centered=True)
+    # id: (config, environment, build_gemma3_gguf keywords, report keys that must be there)
+    return {"mini4b-q4_0-f16": ("mini-4b", {}, {}, ("prefill_gemm16_gate_up", "prefill_gemm16_down", "gemv_qkv")),
+            # (GEMM v7 takes only launches that fill the chip twice over, none at 40 tokens: forced, as in
+            # test_ops_prefill_f16_gemm)
+            "mini4b-q4_0-f16-v7": ("mini-4b", {"LLMI_PG7": "128x64"}, {}, ("prefill_gemm16_gate_up", "prefill_gemm16_down")),
+            "mini4b-q4_0-int8": ("mini-4b", {"LLMI_PREFILL_F16": "0"}, {}, ("prefill_gemm_gate_up", "prefill_gemm_down")),
+            "mini1b-q8_0": ("mini-1b", {}, dict(wtype=TT.Q8_0), ("prefill_gemm_qkv", "prefill_gemm_down")),
+            "mini27b-q4_0": ("mini-27b", {}, {}, ("prefill_gemm16_gate_up", "gemv_qkv")),
+            "mini4b-q4_k_m": ("mini-4b", {}, kq, ("prefill_gemm_qkv", "prefill_gemm_down", "gemv_qkv", "gemv_o", "gemv_down"))}
+
+
+@pytest.mark.parametrize("case", ["mini4b-q4_0-f16", "mini4b-q4_0-f16-v7", "mini4b-q4_0-int8", "mini1b-q8_0", "mini27b-q4_0", "mini4b-q4_k_m"])
+def test_ops_edge_scales(oracle, monkeypatch, case):
+    """The decode graph and the prefill GEMMs on scales="edge" weights (synthetic.SCALE_PROFILES: every scale field's
+    sign random; zero, subnormal and smallest-normal d; whole blocks of the quant extremes) -- where the layouts
+    handle the scale by hand: the slab-major Q4_0 of the layer launches, 16 (n - 8) with d / 16 in the int8 GEMM
+    (v5), the f16 dequantization to d (q - 8) of GEMM v6 and (forced) v7, Q8_0's W8 entries, the kq layout's scale words of the
+    Q4_K / Q6_K launches.  A 40-token prompt, then 2 decode steps and a full-logits step, op by op against the oracle
+    from the device's own inputs, oplevel.py's tolerances unchanged."""
+    cfg_name, env, gkw, keys = _edge_cases()[case]
+    chk = _run(oracle, cfg_name, 51, 40, 2, 128, monkeypatch, env, swa_pattern=[True, False], scales="edge", **gkw)
+    for k in keys:
+        assert k in chk.report, k
+
+
+def test_ops_prefill_nongemm_mini4b_signed_scales(oracle):
+    """The non-GEMM prefill kernels do not read weights; with scales="signed" their inputs come from sign-balanced
+    projections: a second operating point at the first case's shape."""
+    _run_pf(oracle, "mini-4b", 47, 70, 0, 128, merge=True, scales="signed")
+
+
 @pytest.mark.parametrize("vtype", ["q6_k", "q4_k"])
 def test_ops_prefill_kquant_int8(oracle, vtype):
     """The default K-quant batched prefill: Q8_K activation blocks from the norm / attention / GELU producers
