@@ -358,6 +358,46 @@ int llmi_session_batch_generate_lookup(llmi_session* s, const int32_t* hist, con
                                        const int32_t* slots, const int32_t* pos, int B, const llmi_lookup* lk,
                                        int max_steps, const int32_t* stop, int n_stop, int32_t* out, int32_t* n_out,
                                        llmi_lookup_stats* stats);
+/* Lookup decoding for sampled rows: everything above holds -- the draft rule, the wrap-around,
+ * nd = min(D, remaining-1), the cut after a stop id, the cut at `remaining` -- with one substitution.  For span row j
+ * of row b, running at position p + j, a[j] is
+ *   - samplers[b].temperature > 0: the sampling rule of llmi_session_set_sampler applied to that token row's full
+ *     logits (after the final soft-cap) with samplers[b] and pos = p + j;
+ *   - samplers[b].temperature == 0: the fused scorer's arg-max, as in llmi_session_batch_generate_lookup.
+ * Emit a[0]; for j >= 1 emit a[j] while d[j-1] == a[j-1].  The draw depends on the position of the token row, not on a
+ * step counter or a generator's state, so a[j] is the id llmi_session_batch_generate_sampled emits at p + j whenever the
+ * tokens before it are the ones that loop ran: a draft token is right exactly when it equals that id, and accepting is
+ * an equality -- no rejection rule, no tolerance, no change of distribution.
+ * Contract (no tolerance): under the row contract on the slots' K/V, out[b] equals row b's ids of
+ * llmi_session_batch_generate_sampled(first = the row's last history token, slots, pos, n_steps = max_new, stop,
+ * samplers) on the same state, up to and including the row's stop id -- whatever the histories, draft_len, the n-gram
+ * bounds, B, the other rows and their samplers, the row order, LLMI_LOOKUP_SYNC and LLMI_LOOKUP_NO_GATHER.  The K/V
+ * rows, the stale-row bound, the GEMM-switch condition and stats are those of llmi_session_batch_generate_lookup.
+ * Only the live token rows of sampled rows need logits: each step the device lists them and a gathered form of the
+ * multi-row logits GEMV reads the F16 table once per llmi_logits_rows_rb(n_embd) listed rows, LLMI_SEQ_MAX rows per
+ * launch; the host never reads the count.  LLMI_LOOKUP_NO_GATHER=1 (environment, read at the call): the logits of all
+ * B (draft_len + 1) token rows, without the list -- the same ids; table widths llmi_logits_rows does not take run this
+ * way too, row by row.  The fused scorer runs only when some row is greedy; when every row is, the launches are
+ * llmi_session_batch_generate_lookup's.
+ * Checks: those of llmi_session_batch_generate_lookup; samplers NULL: LLMI_E_ARG; each sampler as
+ * llmi_session_batch_generate_sampled validates it (the message names the field and the row). */
+int llmi_session_batch_generate_lookup_sampled(llmi_session* s, const int32_t* hist, const int32_t* hist_len,
+                                               const int32_t* slots, const int32_t* pos, int B, const llmi_lookup* lk,
+                                               int max_steps, const int32_t* stop, int n_stop,
+                                               const llmi_sampler* samplers, int32_t* out, int32_t* n_out,
+                                               llmi_lookup_stats* stats);
+/* op level, host pointers, synchronous: the gathered multi-row logits GEMV alone (+ the soft-cap over the listed rows).
+ * x16 [T][E], w16 [V][E] as llmi_logits_rows; idx: n_idx activation-row indices in [0, T) (any order, repeats allowed),
+ * 0 <= n_idx <= cap <= LLMI_SEQ_MAX; logits: [cap][V], read and written: logits[i] (i < n_idx) carries the bits
+ * llmi_logits_rows gives row idx[i]; the rows at and past n_idx come back as they went in. */
+int llmi_logits_rows_gather(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                            const int32_t* idx, int n_idx, int cap, float* logits);
+/* op level, host pointers, synchronous: the sampler's two launches over R <= LLMI_BATCH_TOKENS_MAX logits rows [R][V],
+ * in the lookup loop's chunks of LLMI_SEQ_MAX rows.  Row r draws with samplers[sampler_of_row[r]] (indices in
+ * [0, LLMI_SEQ_MAX); each sampler named needs temperature > 0) at position pos[r]: ids[r] = llmi_sample_logits' token
+ * for that row; pos[r] < 0 (an ended row): ids[r] = -1. */
+int llmi_sample_logits_rows(const float* logits, int R, int V, const llmi_sampler* samplers,
+                            const int32_t* sampler_of_row, const int32_t* pos, int32_t* ids);
 /* op level, host pointers, synchronous: the draft rule alone, by the same kernel.  draft: draft_len entries;
  * *n_draft = the tokens drafted (0: no match; else draft_len), *match_end = e (-1: none), *match_len = ml(e)
  * (each may be NULL).  L >= 1, 1 <= draft_len <= 31, 1 <= ngram_min <= ngram_max <= 8. */
@@ -460,7 +500,13 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *  13 = lookup_step_kernel's draft search (+ the step's tables) over the rows of the most recent
  *       llmi_session_batch_generate_lookup call, with that call's parameters, every row searched whatever is left of
  *       its budget, no state changed; bytes = the history tokens read, 4 bytes x the sum of the rows' history lengths
- *       as the call left them (0 / 0 before any lookup step).
+ *       as the call left them (0 / 0 before any lookup step);
+ *  14 = the sampled lookup loop's selection over the token rows of the most recent step of
+ *       llmi_session_batch_generate_lookup_sampled that had a live sampled row: the live-row list, the gathered logits
+ *       GEMV's chunks, the soft-cap, the sampler's select and finalize launches, into a list and ids of its own (no
+ *       state changed); bytes = ceil(n_live / llmi_logits_rows_rb(n_embd)) x the F16 table plus the n_live x vocab f32
+ *       logits (after a call under LLMI_LOOKUP_NO_GATHER=1: one read per block of every chunk's token rows, and all
+ *       B (draft_len + 1) rows' logits); 0 / 0 before any such step.
  * Returns the mean microseconds and the mean algorithmic bytes per launch
  * (0 / 0 when the family does not exist on this session). */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);

@@ -133,6 +133,11 @@ _SIGS = {
                                                       C.POINTER(Sampler), _vp]),
     "llmi_session_batch_generate_lookup": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(Lookup), C.c_int, _vp,
                                                      C.c_int, _vp, _vp, C.POINTER(LookupStats)]),
+    "llmi_session_batch_generate_lookup_sampled": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(Lookup), C.c_int,
+                                                             _vp, C.c_int, C.POINTER(Sampler), _vp, _vp,
+                                                             C.POINTER(LookupStats)]),
+    "llmi_logits_rows_gather": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, C.c_int, C.c_int, _vp]),
+    "llmi_sample_logits_rows": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Sampler), _vp, _vp, _vp]),
     "llmi_lookup_draft": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(C.c_int),
                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "llmi_logits_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp]),

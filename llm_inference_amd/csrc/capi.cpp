@@ -508,6 +508,133 @@ int llmi_session_batch_generate_lookup(llmi_session* s, const int32_t* hist, con
   });
 }
 
+int llmi_session_batch_generate_lookup_sampled(llmi_session* s, const int32_t* hist, const int32_t* hist_len,
+                                               const int32_t* slots, const int32_t* pos, int B, const llmi_lookup* lk,
+                                               int max_steps, const int32_t* stop, int n_stop,
+                                               const llmi_sampler* samplers, int32_t* out, int32_t* n_out,
+                                               llmi_lookup_stats* stats) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer");
+    if (!hist) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (hist)");
+    if (!hist_len) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (hist_len)");
+    if (!slots) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (slots)");
+    if (!pos) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (pos)");
+    if (!lk) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (lk)");
+    if (!samplers) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (samplers)");
+    if (!out) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (out)");
+    if (!n_out) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (n_out)");
+    s->s->batch_generate_lookup_sampled(hist, hist_len, slots, pos, B, *lk, max_steps, stop, n_stop, samplers, out,
+                                        n_out, stats);
+  });
+}
+
+int llmi_logits_rows_gather(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                            const int32_t* idx, int n_idx, int cap, float* logits) {
+  return guard([&] {
+    if (!x16 || !w16 || !logits) throw status_error(LLMI_E_ARG, "logits_rows_gather: null pointer");
+    if (T <= 0 || V <= 0) throw status_error(LLMI_E_ARG, "logits_rows_gather: T and V must be positive");
+    if (logits_rows_rb(E) == 0)
+      throw status_error(LLMI_E_SIZE, "logits_rows_gather: E must be a multiple of 128, at most 6144");
+    if (cap < 1 || cap > LLMI_SEQ_MAX)
+      throw status_error(LLMI_E_RANGE, "logits_rows_gather: cap must be in 1.." + std::to_string(LLMI_SEQ_MAX) + " (cap)");
+    if (n_idx < 0 || n_idx > cap) throw status_error(LLMI_E_RANGE, "logits_rows_gather: n_idx must be in 0..cap (n_idx)");
+    if (n_idx > 0 && !idx) throw status_error(LLMI_E_ARG, "logits_rows_gather: null pointer (idx)");
+    for (int i = 0; i < n_idx; i++)
+      if (idx[i] < 0 || idx[i] >= T) throw status_error(LLMI_E_RANGE, "logits_rows_gather: row index outside [0, T) (idx)");
+    Ctx& c = ctx();
+    const size_t xb = (size_t)T * E * 2, wb = (size_t)V * E * 2, ob = (size_t)cap * V * 4;
+    uint16_t* xd = (uint16_t*)c.get(0, xb);
+    uint16_t* wd = (uint16_t*)c.get(1, wb);
+    float* od = (float*)c.get(2, ob);
+    int32_t* list = (int32_t*)c.get(3, (size_t)(cap + 1) * 4);  // the list, then its count
+    LLMI_HIP(hipMemcpyAsync(xd, x16, xb, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(wd, w16, wb, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(od, logits, ob, hipMemcpyHostToDevice, c.stream));  // (the caller's rows past n_idx stay)
+    if (n_idx > 0) LLMI_HIP(hipMemcpyAsync(list, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(list + cap, &n_idx, 4, hipMemcpyHostToDevice, c.stream));
+    DevWeight w;
+    w.type = T_F16;
+    w.rows = V;
+    w.cols = E;
+    w.qs = wd;
+    w.bytes = wb;
+    launch_gemv_f16_rows_gather(w, xd, E, list, list + cap, 0, cap, od, c.stream);
+    if (softcap > 0.0f) launch_softcap_live_rows(od, V, cap, list + cap, 0, softcap, c.stream);
+    LLMI_HIP(hipMemcpyAsync(logits, od, ob, hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipStreamSynchronize(c.stream));
+  });
+}
+
+int llmi_sample_logits_rows(const float* logits, int R, int V, const llmi_sampler* samplers,
+                            const int32_t* sampler_of_row, const int32_t* pos, int32_t* ids) {
+  return guard([&] {
+    if (!logits || !samplers || !sampler_of_row || !pos || !ids)
+      throw status_error(LLMI_E_ARG, "sample_logits_rows: null pointer");
+    if (R < 1 || R > LLMI_BATCH_TOKENS_MAX)
+      throw status_error(LLMI_E_RANGE, "sample_logits_rows: R must be in 1.." + std::to_string(LLMI_BATCH_TOKENS_MAX) + " (R)");
+    int ept = 0;
+    if (V < 1 || sample_groups(V, &ept) == 0)
+      throw status_error(LLMI_E_SIZE, "sample_logits_rows: between 1 and 1,048,576 logits");
+    int n_samplers = 0;  // the samplers the rows name: 0 .. the largest index
+    for (int r = 0; r < R; r++) {
+      if (sampler_of_row[r] < 0 || sampler_of_row[r] >= LLMI_SEQ_MAX)
+        throw status_error(LLMI_E_RANGE, "sample_logits_rows: sampler index outside [0, " + std::to_string(LLMI_SEQ_MAX) +
+                                             ") (sampler_of_row)");
+      n_samplers = std::max(n_samplers, sampler_of_row[r] + 1);
+    }
+    std::vector<SamplerDev> sp((size_t)n_samplers);
+    for (int b = 0; b < n_samplers; b++) {
+      try {
+        validate_sampler(samplers[b]);
+        if (!(samplers[b].temperature > 0.0f)) throw status_error(LLMI_E_ARG, "temperature must be > 0");
+      } catch (const status_error& e) {
+        throw status_error(e.code, std::string("sample_logits_rows: ") + e.what() + " (samplers[" + std::to_string(b) + "])");
+      }
+      sp[(size_t)b] = SamplerDev{samplers[b].temperature, samplers[b].top_k == 0 ? LLMI_SAMPLE_MAX_K : samplers[b].top_k,
+                                 samplers[b].top_p, 0, samplers[b].seed};
+    }
+    std::vector<SeqRow> rows((size_t)R);
+    std::vector<int32_t> list((size_t)R + 1), res((size_t)R, -1);
+    for (int r = 0; r < R; r++) {
+      rows[(size_t)r] = SeqRow{0, pos[r]};
+      list[(size_t)r] = r;
+    }
+    list[(size_t)R] = R;
+    Ctx& c = ctx();
+    const int CH = LLMI_SEQ_MAX;
+    float* ld = (float*)c.get(0, (size_t)R * V * 4);
+    auto* surv = (unsigned long long*)c.get(1, (size_t)std::min(R, CH) * SAMPLE_MAX_GROUPS * SAMPLE_MAX_K * 8);
+    // slot 2: the samplers, then per row the token row, the sampler index, the list (+ count) and the id
+    const size_t sp_bytes = (size_t)LLMI_SEQ_MAX * sizeof(SamplerDev);
+    uint8_t* misc = (uint8_t*)c.get(2, sp_bytes + (size_t)R * 20 + 16);
+    auto* spd = (SamplerDev*)misc;
+    auto* rd = (SeqRow*)(misc + sp_bytes);
+    int32_t* ofd = (int32_t*)(misc + sp_bytes + (size_t)R * 8);
+    int32_t* idd = (int32_t*)(misc + sp_bytes + (size_t)R * 12);
+    int32_t* lid = (int32_t*)(misc + sp_bytes + (size_t)R * 16);
+    LLMI_HIP(hipMemcpyAsync(ld, logits, (size_t)R * V * 4, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(spd, sp.data(), sp.size() * sizeof(SamplerDev), hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(rd, rows.data(), (size_t)R * 8, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(ofd, sampler_of_row, (size_t)R * 4, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(idd, res.data(), (size_t)R * 4, hipMemcpyHostToDevice, c.stream));
+    LLMI_HIP(hipMemcpyAsync(lid, list.data(), ((size_t)R + 1) * 4, hipMemcpyHostToDevice, c.stream));
+    TokenRowsArgs a;
+    a.n_live = lid + R;
+    a.sp = spd;
+    a.sp_of = ofd;
+    a.trows = rd;
+    for (int c0 = 0; c0 < R; c0 += CH) {  // the session's chunks: LLMI_SEQ_MAX compact rows per launch
+      a.idx = lid + c0;
+      a.base = c0;
+      a.cap = std::min(CH, R - c0);
+      launch_sample_select_token_rows(ld + (size_t)c0 * V, V, a, surv, c.stream);
+      launch_sample_finalize_token_rows(surv, V, a, idd, c.stream);
+    }
+    LLMI_HIP(hipMemcpyAsync(ids, idd, (size_t)R * 4, hipMemcpyDeviceToHost, c.stream));
+    LLMI_HIP(hipStreamSynchronize(c.stream));
+  });
+}
+
 int llmi_lookup_draft(const int32_t* hist, int L, int ngram_max, int ngram_min, int draft_len, int32_t* draft,
                       int* n_draft, int* match_end, int* match_len) {
   return guard([&] {

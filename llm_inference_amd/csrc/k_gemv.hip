@@ -318,54 +318,71 @@ __global__ __launch_bounds__(256) void gemv_f16_rows_pipe(const uint4* __restric
 // `lane < T ? t : 0`, the same wave_sum -- so out[r][row] carries the bits launch_gemv(GEMV_FAST) writes for row r
 // alone.  The table is read once per row block, with the next table row's loads in flight as in the pipe kernel.
 // RB = logits_rows_rb(cols) (kernels.h): the block's rows must fit 64 KB of LDS and LDS must keep up with HBM.
+// The gathered form below (the lookup loop's live rows) differs in one expression only, the
+// activation row that output row r0 + r reads, so the body is one text, expanded in both kernels with that expression:
+// the kernel here stays, token for token, what it was before the gathered form existed.
+#define LLMI_GEMV_F16_ROWS_MULTI_BODY(XROW)                                                                        \
+  constexpr int NP = P + (T ? 1 : 0);                                                                              \
+  constexpr int RU4 = P * 64 + T; /* uint4 per row */                                                              \
+  extern __shared__ uint4 xs[];   /* [RB][RU4] */                                                                  \
+  const int lane = threadIdx.x & 63;                                                                               \
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);                                                            \
+  const int nwaves = gridDim.x * 4;                                                                                \
+  const int tl = T ? lane % (T ? T : 64) : lane;                                                                   \
+  const int r0 = blockIdx.y * RB;                                                                                  \
+  const int nr = min(RB, R - r0);                                                                                  \
+  for (int i = threadIdx.x; i < nr * RU4; i += 256) {                                                              \
+    const int r = i / RU4;                                                                                         \
+    xs[i] = x16[(size_t)(XROW) * xstride4 + (i - r * RU4)];                                                        \
+  }                                                                                                                \
+  __syncthreads();                                                                                                 \
+  auto load_row = [&](uint4 (&v)[NP], int row) {                                                                   \
+    const uint4* wr = w + (size_t)row * RU4;                                                                       \
+    _Pragma("unroll") for (int p = 0; p < NP; p++) v[p] = ld_nt(wr + p * 64 + (p < P ? lane : tl));                \
+  };                                                                                                               \
+  int row = wave;                                                                                                  \
+  uint4 cur[NP];                                                                                                   \
+  load_row(cur, min(row, rows - 1));                                                                               \
+  for (; row < rows; row += nwaves) {                                                                              \
+    uint4 nxt[NP];                                                                                                 \
+    load_row(nxt, min(row + nwaves, rows - 1)); /* clamped: the last one re-reads a row just read */               \
+    _Pragma("unroll") for (int r = 0; r < RB; r++) {                                                               \
+      if (r < nr) { /* (uniform over the work-group) */                                                            \
+        const uint4* xr = xs + r * RU4;                                                                            \
+        float acc = 0.0f;                                                                                          \
+        _Pragma("unroll") for (int p = 0; p < P; p++) acc = dot8_f16(cur[p], xr[p * 64 + lane], acc);              \
+        if constexpr (T != 0) {                                                                                    \
+          const float t = dot8_f16(cur[P], xr[P * 64 + tl], 0.0f);                                                 \
+          acc += lane < T ? t : 0.0f;                                                                              \
+        }                                                                                                          \
+        acc = wave_sum(acc);                                                                                       \
+        if (lane == 0) out[(size_t)(r0 + r) * rows + row] = acc;                                                   \
+      }                                                                                                            \
+    }                                                                                                              \
+    _Pragma("unroll") for (int p = 0; p < NP; p++) cur[p] = nxt[p];                                                \
+  }
+
 template <int P, int T, int RB>
 __global__ __launch_bounds__(256) void gemv_f16_rows_multi(const uint4* __restrict__ w, int rows,
                                                            const uint4* __restrict__ x16, int xstride4, int R,
                                                            float* __restrict__ out) {
-  constexpr int NP = P + (T ? 1 : 0);
-  constexpr int RU4 = P * 64 + T;  // uint4 per row
-  extern __shared__ uint4 xs[];    // [RB][RU4]
-  const int lane = threadIdx.x & 63;
-  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int nwaves = gridDim.x * 4;
-  const int tl = T ? lane % (T ? T : 64) : lane;
-  const int r0 = blockIdx.y * RB;
-  const int nr = min(RB, R - r0);
-  for (int i = threadIdx.x; i < nr * RU4; i += 256) {
-    const int r = i / RU4;
-    xs[i] = x16[(size_t)(r0 + r) * xstride4 + (i - r * RU4)];
-  }
-  __syncthreads();
-  auto load_row = [&](uint4 (&v)[NP], int row) {
-    const uint4* wr = w + (size_t)row * RU4;
-#pragma unroll
-    for (int p = 0; p < NP; p++) v[p] = ld_nt(wr + p * 64 + (p < P ? lane : tl));
-  };
-  int row = wave;
-  uint4 cur[NP];
-  load_row(cur, min(row, rows - 1));
-  for (; row < rows; row += nwaves) {
-    uint4 nxt[NP];
-    load_row(nxt, min(row + nwaves, rows - 1));  // clamped: the last one re-reads a row just read
-#pragma unroll
-    for (int r = 0; r < RB; r++) {
-      if (r < nr) {  // (uniform over the work-group)
-        const uint4* xr = xs + r * RU4;
-        float acc = 0.0f;
-#pragma unroll
-        for (int p = 0; p < P; p++) acc = dot8_f16(cur[p], xr[p * 64 + lane], acc);
-        if constexpr (T != 0) {
-          const float t = dot8_f16(cur[P], xr[P * 64 + tl], 0.0f);
-          acc += lane < T ? t : 0.0f;
-        }
-        acc = wave_sum(acc);
-        if (lane == 0) out[(size_t)(r0 + r) * rows + row] = acc;
-      }
-    }
-#pragma unroll
-    for (int p = 0; p < NP; p++) cur[p] = nxt[p];
-  }
+  LLMI_GEMV_F16_ROWS_MULTI_BODY(r0 + r)
 }
+
+// The gathered form: compact rows base .. base + cap - 1 of a device list of *n_live activation-row indices (idx points
+// at entry `base`), out [cap][rows].  The rows at and past the count are not written, and a work-group whose row block
+// lies wholly there returns before it issues any table load.
+template <int P, int T, int RB>
+__global__ __launch_bounds__(256) void gemv_f16_rows_gather(const uint4* __restrict__ w, int rows,
+                                                            const uint4* __restrict__ x16, int xstride4,
+                                                            const int32_t* __restrict__ idx,
+                                                            const int32_t* __restrict__ n_live, int base, int cap,
+                                                            float* __restrict__ out) {
+  const int R = min(cap, *n_live - base);
+  if ((int)blockIdx.y * RB >= R) return;
+  LLMI_GEMV_F16_ROWS_MULTI_BODY(idx[r0 + r])
+}
+#undef LLMI_GEMV_F16_ROWS_MULTI_BODY
 
 // fast, general cols (cols % 8 == 0): flat (row, chunk) items like Q4_0.
 template <int R, int P>
@@ -904,6 +921,35 @@ void launch_gemv_f16_rows(const DevWeight& w, const uint16_t* x16, int xstride, 
     const dim3 grid((waves + 3) / 4, (R + RB - 1) / RB);                                                           \
     hipLaunchKernelGGL((gemv_f16_rows_multi<PP, TT, RB>), grid, dim3(256), (size_t)RB * (PP * 64 + TT) * 16, s,    \
                        (const uint4*)w.qs, rows, (const uint4*)x16, xstride / 8, R, out);                          \
+    break;                                                                                                         \
+  }
+#define LLMI_F16M4(PP) LLMI_F16M(PP, 0) LLMI_F16M(PP, 16) LLMI_F16M(PP, 32) LLMI_F16M(PP, 48)
+    LLMI_F16M(0, 16) LLMI_F16M(0, 32) LLMI_F16M(0, 48) LLMI_F16M4(1) LLMI_F16M4(2) LLMI_F16M4(3) LLMI_F16M4(4)
+    LLMI_F16M4(5) LLMI_F16M4(6) LLMI_F16M4(7) LLMI_F16M4(8) LLMI_F16M4(9) LLMI_F16M4(10) LLMI_F16M4(11)
+    LLMI_F16M(12, 0)
+#undef LLMI_F16M4
+#undef LLMI_F16M
+  }
+  LLMI_HIP(hipGetLastError());
+}
+
+void launch_gemv_f16_rows_gather(const DevWeight& w, const uint16_t* x16, int xstride, const int32_t* idx,
+                                 const int32_t* n_live, int base, int cap, float* out, hipStream_t s) {
+  if (w.type != T_F16 || logits_rows_rb(w.cols) == 0)
+    throw std::runtime_error("gemv_f16_rows_gather: an F16 table with cols % 128 == 0 and cols <= 6144");
+  if (xstride < w.cols || xstride % 8 != 0) throw std::runtime_error("gemv_f16_rows_gather: x row stride");
+  if (!idx || !n_live || base < 0) throw std::runtime_error("gemv_f16_rows_gather: the device list");
+  const int rows = w.rows;
+  if (rows == 0 || cap <= 0) return;
+  const int u4 = w.cols / 8, P = u4 / 64, T = u4 % 64;
+  const int waves = std::min(rows, w.cols >= 2560 ? 256 * 8 : 256 * 16);  // launch_gemv's
+  switch (P * 4 + T / 16) {
+#define LLMI_F16M(PP, TT)                                                                                          \
+  case PP * 4 + TT / 16: {                                                                                         \
+    constexpr int RB = logits_rows_rb((PP * 64 + TT) * 8);                                                         \
+    const dim3 grid((waves + 3) / 4, (cap + RB - 1) / RB);                                                         \
+    hipLaunchKernelGGL((gemv_f16_rows_gather<PP, TT, RB>), grid, dim3(256), (size_t)RB * (PP * 64 + TT) * 16, s,   \
+                       (const uint4*)w.qs, rows, (const uint4*)x16, xstride / 8, idx, n_live, base, cap, out);     \
     break;                                                                                                         \
   }
 #define LLMI_F16M4(PP) LLMI_F16M(PP, 0) LLMI_F16M(PP, 16) LLMI_F16M(PP, 32) LLMI_F16M(PP, 48)

@@ -3,6 +3,10 @@
 // drafts the next step's tokens by n-gram lookup in the history and writes the next step's device tables (token ids,
 // one SeqRow per token row, one AttnBlock per row).  One work-group per row; plain vector stores only, no global
 // atomics and no cross-work-group waits -- a row's state is touched by its own work-group alone.
+// For sampled rows (llmi_session_batch_generate_lookup_sampled; section 16) the same launch accepts against the rows'
+// seeded draws, and two small launches serve the logits those draws need: the list of the step's live token rows and
+// the final soft-cap over that list.
+#include "sample.h"
 #include "session_kernels.h"
 
 namespace llmi {
@@ -126,6 +130,70 @@ void launch_lookup_step(const LookupArgs& a, hipStream_t s) {
       a.ngram_max > LOOKUP_NGRAM_MAX || a.n_stop < 0 || a.n_stop > 4 || a.max_new < 1)
     throw std::runtime_error("lookup_step: 1 <= draft_len <= 31, 1 <= ngram_min <= ngram_max <= 8, n_stop <= 4");
   hipLaunchKernelGGL(lookup_step_kernel, dim3(a.B), dim3(256), 0, s, a);
+  LLMI_HIP(hipGetLastError());
+}
+
+// ---- sampled rows ----
+// The live-row list of the step whose tables lookup_step_kernel has written: thread t owns token row t; an inclusive
+// scan of the live flags (waves by shuffle, the 8 wave totals through LDS) gives each live row its place, so the list
+// is in token-row order and nothing depends on arrival order.  One work-group: T <= 512.
+__global__ __launch_bounds__(512) void lookup_live_rows_kernel(LiveRowsArgs a) {
+  __shared__ int sh_wave[8];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  SeqRow sr;
+  sr.slot = 0;
+  sr.pos = -1;
+  bool sampled = false;
+  if (t < a.T) {
+    sr = a.trows[t];
+    sampled = a.sp[t / a.W].temperature > 0.0f;
+  }
+  const bool run = sr.pos >= 0;
+  const int live = (t < a.T && (a.all || (run && sampled))) ? 1 : 0;
+  const int n_sampling = __syncthreads_count(run && sampled);  // (the snapshot's condition, whatever a.all)
+  int inc = live;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int x = __shfl_up(inc, o);
+    if (lane >= o) inc += x;
+  }
+  if (lane == 63) sh_wave[wave] = inc;
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) {
+    before += w < wave ? sh_wave[w] : 0;
+    total += sh_wave[w];
+  }
+  if (live) a.idx[before + inc - 1] = t;
+  if (t == 0) *a.n_live = total;
+  if (t < a.T) {
+    if (run && !sampled && a.argmax) a.ids[t] = a.argmax[t];
+    if (a.snap && n_sampling > 0) a.snap[t] = sr;
+  }
+}
+
+void launch_lookup_live_rows(const LiveRowsArgs& a, hipStream_t s) {
+  if (a.T < 1 || a.T > 512 || a.W < 1 || a.T % a.W != 0)
+    throw std::runtime_error("lookup_live_rows: 1 <= T <= 512 token rows, W rows per sampler");
+  hipLaunchKernelGGL(lookup_live_rows_kernel, dim3(1), dim3(512), 0, s, a);
+  LLMI_HIP(hipGetLastError());
+}
+
+// softcap_kernel (k_session.hip) over the compact rows below the device count; a work-group past it returns at once
+__global__ __launch_bounds__(256) void softcap_live_rows_kernel(float* __restrict__ x, int V, int rows,
+                                                                const int32_t* __restrict__ n_live, int base,
+                                                                float cap) {
+  if ((int)blockIdx.y >= min(rows, *n_live - base)) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  float* xr = x + (size_t)blockIdx.y * V;
+  if (i < V) xr[i] = cap * llmi_glibc::tanhf(xr[i] / cap);
+}
+
+void launch_softcap_live_rows(float* x, int V, int rows, const int32_t* n_live, int base, float cap, hipStream_t s) {
+  if (V < 1 || rows < 1 || rows > 65535) throw std::runtime_error("softcap_live_rows: 1 <= rows <= 65535");
+  hipLaunchKernelGGL(softcap_live_rows_kernel, dim3((V + 255) / 256, rows), dim3(256), 0, s, x, V, rows, n_live, base,
+                     cap);
   LLMI_HIP(hipGetLastError());
 }
 

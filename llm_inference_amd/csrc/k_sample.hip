@@ -1,6 +1,7 @@
 // k_sample.hip -- the sampler's two launches (sample.h): the multi-work-group candidate
 // selection over a logits row and the one-work-group finalize with the token feedback.  The decode loop's folded
-// form of the finalize (with the next step's embed_norm) is in k_session.hip.
+// form of the finalize (with the next step's embed_norm) is in k_session.hip.  The batch loop's rows (section 13) and
+// the lookup loop's token rows (section 16) are the same two blocks over many logits rows.
 #include "sample.h"
 #include "session_kernels.h"
 
@@ -169,6 +170,69 @@ void launch_sample_finalize_rows(const unsigned long long* surv, int V, int B, c
   if (B < 1 || B > 64) throw std::runtime_error("sample_finalize_rows: 1 <= B <= 64");
   hipLaunchKernelGGL(sample_finalize_rows_kernel, dim3(B), dim3(SAMPLE_THREADS), 0, s, surv, g * SAMPLE_MAX_K, sp,
                      argmax, rows, tokens, stops, out, feedback ? 1 : 0);
+  LLMI_HIP(hipGetLastError());
+}
+
+// ---- the lookup loop's token rows ----
+// Compact row i of the launch (logits row i, survivors surv[i]) is token row t = idx[i] of the step, with the sampler
+// *q and the position trows[t].pos.  The rows at and past the device count, ended token rows and greedy rows' token
+// rows leave at once.  -1: none
+__device__ __forceinline__ int sample_token_row(int i, const TokenRowsArgs& a, const SamplerDev** q) {
+  if (i >= min(a.cap, *a.n_live - a.base)) return -1;
+  const int t = a.idx[i];
+  *q = a.sp + (a.sp_of ? a.sp_of[t] : t / a.W);
+  if (a.trows[t].pos < 0 || (*q)->temperature == 0.0f) return -1;
+  return t;
+}
+
+template <int EPT>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_select_token_rows_kernel(const float* __restrict__ logits,
+                                                                                  int V, TokenRowsArgs a,
+                                                                                  unsigned long long* __restrict__ surv) {
+  __shared__ SampleShared sh;
+  const SamplerDev* q = nullptr;
+  const int i = blockIdx.y, t = sample_token_row(i, a, &q);
+  if (t < 0) return;
+  sample_select_block<EPT>(logits + (size_t)i * V, V, q, surv + (size_t)i * SAMPLE_MAX_GROUPS * SAMPLE_MAX_K, sh);
+}
+
+void launch_sample_select_token_rows(const float* logits, int V, const TokenRowsArgs& a, unsigned long long* surv,
+                                     hipStream_t s) {
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  if (a.cap < 1 || a.cap > 512 || a.W < 1) throw std::runtime_error("sample_select_token_rows: 1 <= cap <= 512");
+  const dim3 grid(g, a.cap);
+  if (ept == 4)
+    hipLaunchKernelGGL(sample_select_token_rows_kernel<4>, grid, dim3(SAMPLE_THREADS), 0, s, logits, V, a, surv);
+  else if (ept == 8)
+    hipLaunchKernelGGL(sample_select_token_rows_kernel<8>, grid, dim3(SAMPLE_THREADS), 0, s, logits, V, a, surv);
+  else
+    hipLaunchKernelGGL(sample_select_token_rows_kernel<16>, grid, dim3(SAMPLE_THREADS), 0, s, logits, V, a, surv);
+  LLMI_HIP(hipGetLastError());
+}
+
+// Work-group i: ids[t] = sample_finalize_block on compact row i's survivors at pos = trows[t].pos.  No token feedback:
+// lookup_step_kernel reads ids where the greedy loop reads the scorer's arg-max.
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_finalize_token_rows_kernel(
+    const unsigned long long* __restrict__ surv, int n_surv, TokenRowsArgs a, int32_t* __restrict__ ids) {
+  __shared__ SampleShared sh;
+  const SamplerDev* q = nullptr;
+  const int i = blockIdx.x, t = sample_token_row(i, a, &q);
+  if (t < 0) return;
+  const int id = sample_finalize_block(surv + (size_t)i * SAMPLE_MAX_GROUPS * SAMPLE_MAX_K, n_surv, q, a.trows[t].pos,
+                                       nullptr, sh);
+  if (threadIdx.x == 0) ids[t] = id;
+}
+
+void launch_sample_finalize_token_rows(const unsigned long long* surv, int V, const TokenRowsArgs& a, int32_t* ids,
+                                       hipStream_t s) {
+  int ept = 0;
+  const int g = V > 0 ? sample_groups(V, &ept) : 0;
+  if (g == 0) throw std::runtime_error("sample: between 1 and 1,048,576 logits");
+  if (a.cap < 1 || a.cap > 512 || a.W < 1) throw std::runtime_error("sample_finalize_token_rows: 1 <= cap <= 512");
+  hipLaunchKernelGGL(sample_finalize_token_rows_kernel, dim3(a.cap), dim3(SAMPLE_THREADS), 0, s, surv, g * SAMPLE_MAX_K,
+                     a, ids);
   LLMI_HIP(hipGetLastError());
 }
 

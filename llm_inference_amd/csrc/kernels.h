@@ -71,6 +71,13 @@ constexpr int logits_rows_rb(int cols) {
   return (cols <= 0 || cols % 128 != 0 || cols > 6144) ? 0 : cols <= 3840 ? 8 : 4;
 }
 void launch_gemv_f16_rows(const DevWeight& w, const uint16_t* x16, int xstride, int R, float* out, hipStream_t s);
+// The gathered form: a device list of *n_live activation-row indices, of which this launch takes
+// the compact rows base .. base + cap - 1 (idx points at entry `base`): out[i] (i < min(cap, *n_live - base)) carries
+// the bits launch_gemv(GEMV_FAST) writes for activation row idx[i] alone; the other rows of out are not written.  The
+// grid covers cap rows; a work-group whose block of logits_rows_rb(cols) rows lies at or past the count returns before
+// it loads anything from the table, so the table reads follow the count the host never sees.
+void launch_gemv_f16_rows_gather(const DevWeight& w, const uint16_t* x16, int xstride, const int32_t* idx,
+                                 const int32_t* n_live, int base, int cap, float* out, hipStream_t s);
 
 // elementwise / norms
 // o = rms_norm(x) [* w if w]  per row of n, n_rows rows; exact = serial FMA sum
@@ -153,5 +160,27 @@ struct LookupArgs {
   int n_stop = 0;
 };
 void launch_lookup_step(const LookupArgs& a, hipStream_t s);
+
+// ---- lookup decoding for sampled rows (k_lookup.hip, k_sample.hip) ----
+// The step's live-row list, one work-group over the T <= 512 token rows the lookup launch has written: idx[0..n) = the
+// token rows t, ascending, with trows[t].pos >= 0 whose row t / W (W = draft_len + 1) samples (sp[t / W].temperature
+// > 0), *n_live = n.  all: every token row is listed (LLMI_LOOKUP_NO_GATHER: the sampler's launches skip the ended
+// and the greedy ones themselves).  A greedy row's live token rows take ids[t] = argmax[t] (argmax null: the call has
+// no greedy row).  snap non-null: trows[0..T) is copied there when some token row is live and sampled -- the last step
+// that sampled, for time_kernel(14).
+struct SamplerDev;  // (sample.h)
+struct LiveRowsArgs {
+  const SeqRow* trows = nullptr;
+  const SamplerDev* sp = nullptr;
+  int T = 0, W = 1, all = 0;
+  int32_t* idx = nullptr;     // [T]
+  int32_t* n_live = nullptr;  // [1]
+  const int32_t* argmax = nullptr;
+  int32_t* ids = nullptr;     // [T]
+  SeqRow* snap = nullptr;     // [T]
+};
+void launch_lookup_live_rows(const LiveRowsArgs& a, hipStream_t s);
+// x[i][0..V) = cap tanhf(x[i] / cap) (launch_softcap's expression) for the compact rows i < min(rows, *n_live - base)
+void launch_softcap_live_rows(float* x, int V, int rows, const int32_t* n_live, int base, float cap, hipStream_t s);
 
 }  // namespace llmi

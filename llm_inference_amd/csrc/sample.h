@@ -324,6 +324,25 @@ void launch_sample_finalize_rows(const unsigned long long* surv, int V, int B, c
                                  const int32_t* argmax, SeqRow* rows, int32_t* tokens, const BatchStops& stops,
                                  int32_t* out, bool feedback, hipStream_t s);
 
+// The lookup loop's token rows (Session::batch_generate_lookup_sampled): the two launches over
+// `cap` compact rows -- logits [cap][V], survivors [cap][SAMPLE_MAX_GROUPS x 256] -- of a device list.  Compact row i
+// (i < min(cap, *n_live - base); idx points at entry `base`) is token row t = idx[i]: the one-row launches' work on
+// logits row i with sampler sp[sp_of ? sp_of[t] : t / W] at pos = trows[t].pos, its id into ids[t].  A token row with
+// trows[t].pos < 0 has ended and one whose sampler has temperature 0 is greedy (the caller fills its id): both are
+// skipped, as are the rows at and past the count.  No token feedback: lookup_step_kernel reads ids.
+struct TokenRowsArgs {
+  const int32_t* idx = nullptr;
+  const int32_t* n_live = nullptr;
+  int base = 0, cap = 0, W = 1;
+  const SamplerDev* sp = nullptr;
+  const int32_t* sp_of = nullptr;
+  const SeqRow* trows = nullptr;
+};
+void launch_sample_select_token_rows(const float* logits, int V, const TokenRowsArgs& a, unsigned long long* surv,
+                                     hipStream_t s);
+void launch_sample_finalize_token_rows(const unsigned long long* surv, int V, const TokenRowsArgs& a, int32_t* ids,
+                                       hipStream_t s);
+
 // k_session.hip: launch_sample_finalize with the feedback, then the next step's embed_norm (as
 // launch_finalize_embed_norm)
 struct NormOut;

@@ -2355,6 +2355,7 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
   if (which == 11) return time_batch_sampling(reps, us, bytes);
   if (which == 12) return time_extend_attn(reps, us, bytes);
   if (which == 13) return time_lookup_step(reps, us, bytes);
+  if (which == 14) return time_lookup_select(reps, us, bytes);
   if (which == 9) {  // the fused scorer's two launches over the most recently scored chunk (its rows are still there)
     *us = *bytes = 0.0;
     if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;

@@ -98,6 +98,11 @@ class Session {
   void batch_generate_lookup(const int32_t* hist, const int32_t* hist_len, const int32_t* slots, const int32_t* pos,
                              int B, const llmi_lookup& lk, int max_steps, const int32_t* stop, int n_stop, int32_t* out,
                              int32_t* n_out, llmi_lookup_stats* stats);
+  // ... for sampled rows: a draft is accepted against the row's seeded draw at its own position
+  void batch_generate_lookup_sampled(const int32_t* hist, const int32_t* hist_len, const int32_t* slots,
+                                     const int32_t* pos, int B, const llmi_lookup& lk, int max_steps, const int32_t* stop,
+                                     int n_stop, const llmi_sampler* samplers, int32_t* out, int32_t* n_out,
+                                     llmi_lookup_stats* stats);
   // per-row seeded sampling inside the batch loop; samplers: B entries
   void batch_generate_sampled(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                               const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);
@@ -394,6 +399,26 @@ class Session {
   LookupArgs lk_last_{};             // the most recent lookup step's launch (B = 0: none yet)
   double lk_last_bytes_ = 0.0;       // 4 x the rows' history lengths after that call
   void time_lookup_step(int reps, double* us, double* bytes);
+  // the lookup loop: greedy (samplers null: batch_generate_lookup, today's launches) or with a sampler per row
+  void lookup_loop(const char* fn, const int32_t* hist, const int32_t* hist_len, const int32_t* slots, const int32_t* pos,
+                   int B, const llmi_lookup& lk, int max_steps, const int32_t* stop, int n_stop,
+                   const llmi_sampler* samplers, int32_t* out, int32_t* n_out, llmi_lookup_stats* stats);
+  // sampled rows: the ids lookup_step_kernel accepts against, the step's live-row list
+  int32_t* lk_ids_ = nullptr;        // [LLMI_BATCH_TOKENS_MAX] per token row: the seeded draw, or the arg-max (greedy rows)
+  int32_t* lk_live_ = nullptr;       // [LLMI_BATCH_TOKENS_MAX] the live token rows, ascending; [.. + 1]: their count
+  SamplerDev* lk_samplers_ = nullptr;  // [LLMI_SEQ_MAX] the call's per-row samplers
+  SeqRow* lk_snap_ = nullptr;        // [LLMI_BATCH_TOKENS_MAX] the token rows of the last step that sampled
+  int32_t* lk_tids_ = nullptr;       // time_kernel(14)'s ids and list (+ count)
+  int32_t* lk_tlive_ = nullptr;
+  struct LookupSampled {             // the most recent sampled lookup call (T = 0: none yet)
+    int T = 0, W = 1;
+    bool gather = true, any_greedy = false;
+  } lk_samp_;
+  // the selection of one step over the token rows `trows`: the live-row list, the logits of the listed rows in chunks
+  // of LLMI_SEQ_MAX compact rows (gathered, or every token row: LLMI_LOOKUP_NO_GATHER), soft-cap, select, finalize
+  void lookup_select(const SeqRow* trows, int T, int W, bool gather, bool any_greedy, int32_t* live, int32_t* ids,
+                     SeqRow* snap, hipStream_t s);
+  void time_lookup_select(int reps, double* us, double* bytes);
 };
 
 }  // namespace llmi

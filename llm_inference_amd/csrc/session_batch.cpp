@@ -4,7 +4,9 @@
 // sampled loop (section 13) the rows' full logits and the sampler's two multi-row launches.  A ragged step
 // (llmi_session_batch_extend, section 14) carries spans of consecutive tokens: prompt chunks and draft tokens beside
 // decode rows, the attention in its span form.  The lookup loop (llmi_session_batch_generate_lookup, section 15) runs
-// such steps with the tables written on the device: n-gram drafts verified and accepted without leaving it.
+// such steps with the tables written on the device: n-gram drafts verified and accepted without leaving it; with a
+// sampler per row (llmi_session_batch_generate_lookup_sampled, section 16) a draft is accepted against the row's seeded
+// draw, from the logits of the step's live token rows only.
 #include "session.h"
 
 #include <algorithm>
@@ -574,7 +576,66 @@ void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* sl
 void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len, const int32_t* slots,
                                     const int32_t* pos, int B, const llmi_lookup& lk, int max_steps, const int32_t* stop,
                                     int n_stop, int32_t* out, int32_t* n_out, llmi_lookup_stats* stats) {
-  const std::string f = "batch_generate_lookup: ";
+  lookup_loop("batch_generate_lookup", hist, hist_len, slots, pos, B, lk, max_steps, stop, n_stop, nullptr, out, n_out,
+              stats);
+}
+
+// Sampled rows: the sampler is a pure function of a token row's logits, the row's sampler and
+// the token row's position, so the id the sampled batch loop would emit at every position of a draft span is computed
+// for all of the span's rows at once and lookup_step_kernel accepts against those ids in place of the arg-max.  Only
+// the step's live token rows of sampled rows need logits: the device lists them and the gathered GEMV reads the table
+// once per logits_rows_rb of them, LLMI_SEQ_MAX compact rows per launch into bt_logits_.
+void Session::batch_generate_lookup_sampled(const int32_t* hist, const int32_t* hist_len, const int32_t* slots,
+                                            const int32_t* pos, int B, const llmi_lookup& lk, int max_steps,
+                                            const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out,
+                                            int32_t* n_out, llmi_lookup_stats* stats) {
+  if (!samplers) throw status_error(LLMI_E_ARG, "batch_generate_lookup_sampled: null pointer (samplers)");
+  lookup_loop("batch_generate_lookup_sampled", hist, hist_len, slots, pos, B, lk, max_steps, stop, n_stop, samplers, out,
+              n_out, stats);
+}
+
+void Session::lookup_select(const SeqRow* trows, int T, int W, bool gather, bool any_greedy, int32_t* live, int32_t* ids,
+                            SeqRow* snap, hipStream_t s) {
+  const int E = hp_.n_embd;
+  LiveRowsArgs la;
+  la.trows = trows;
+  la.sp = lk_samplers_;
+  la.T = T;
+  la.W = W;
+  la.all = gather ? 0 : 1;
+  la.idx = live;
+  la.n_live = live + LLMI_BATCH_TOKENS_MAX;
+  la.argmax = any_greedy ? sc_amax_ : nullptr;
+  la.ids = ids;
+  la.snap = snap;
+  launch_lookup_live_rows(la, s);
+  TokenRowsArgs ta;
+  ta.n_live = la.n_live;
+  ta.W = W;
+  ta.sp = lk_samplers_;
+  ta.trows = trows;
+  // every chunk is enqueued: the host does not know the count, and a chunk past it costs its work-groups' return
+  for (int c0 = 0; c0 < T; c0 += LLMI_SEQ_MAX) {
+    const int n = std::min(LLMI_SEQ_MAX, T - c0);
+    if (gather) {
+      launch_gemv_f16_rows_gather(logits_w_, sc_x16_, E, live + c0, la.n_live, c0, n, bt_logits_, s);
+      if (hp_.final_softcap > 0.0f) launch_softcap_live_rows(bt_logits_, vocab_, n, la.n_live, c0, hp_.final_softcap, s);
+    } else {  // every token row, listed or not (the list is the identity)
+      batch_logits(n, s, sc_x16_ + (size_t)c0 * E);
+    }
+    ta.idx = live + c0;
+    ta.base = c0;
+    ta.cap = n;
+    launch_sample_select_token_rows(bt_logits_, vocab_, ta, bt_surv_, s);
+    launch_sample_finalize_token_rows(bt_surv_, vocab_, ta, ids, s);
+  }
+}
+
+void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hist_len, const int32_t* slots,
+                          const int32_t* pos, int B, const llmi_lookup& lk, int max_steps, const int32_t* stop,
+                          int n_stop, const llmi_sampler* samplers, int32_t* out, int32_t* n_out,
+                          llmi_lookup_stats* stats) {
+  const std::string f = std::string(fn) + ": ";
   if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
   if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
   if (B < 1 || B > n_seq_) throw status_error(LLMI_E_RANGE, f + "B must be in 1..n_seq (B)");
@@ -618,6 +679,30 @@ void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len
   }
   for (size_t i = 0; i < n_hist; i++)
     if (hist[i] < 0 || hist[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "token id out of range (hist)");
+  std::vector<SamplerDev> sp;
+  bool any_greedy = false, sampled = false;
+  if (samplers) {
+    sp.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+      try {
+        validate_sampler(samplers[b]);
+      } catch (const status_error& e) {
+        throw status_error(e.code, f + e.what() + " (samplers[" + std::to_string(b) + "])");
+      }
+      sp[(size_t)b] = SamplerDev{samplers[b].temperature, samplers[b].top_k == 0 ? LLMI_SAMPLE_MAX_K : samplers[b].top_k,
+                                 samplers[b].top_p, 0, samplers[b].seed};
+      any_greedy = any_greedy || samplers[b].temperature == 0.0f;
+      sampled = sampled || samplers[b].temperature > 0.0f;
+    }
+    int ept = 0;  // (only a row that draws needs the sampler: all-greedy samplers are the greedy call)
+    if (sampled && sample_groups(vocab_, &ept) == 0)
+      throw status_error(LLMI_E_ARG, f + "vocabulary over 1,048,576 rows");
+  }
+  // (samplers that are all greedy: the greedy loop's launches, nothing else)
+  // A/B, read at the call: the logits of every token row, without the list (also the table widths the multi-row
+  // GEMV does not take, through batch_logits' row-by-row path)
+  const char* ng_env = getenv("LLMI_LOOKUP_NO_GATHER");
+  const bool gather = !(ng_env && atoi(ng_env) == 1) && logits_rows_rb(hp_.n_embd) != 0;
   ensure_usable();
   int group = 4;
   if (const char* c = getenv("LLMI_LOOKUP_SYNC")) group = std::max(1, atoi(c));
@@ -643,6 +728,19 @@ void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len
     lk_out_ = dalloc<int32_t>(lk_out_cap_);
   }
   lk_last_.B = 0;  // (until this call has run a step: time_kernel(13) reads the buffers above)
+  if (sampled) {
+    if (!lk_ids_) {
+      lk_ids_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
+      lk_live_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX + 1);
+      lk_snap_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
+      lk_tids_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
+      lk_tlive_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX + 1);
+      lk_samplers_ = dalloc<SamplerDev>(LLMI_SEQ_MAX);
+    }
+    lk_samp_.T = 0;
+    ensure_batch_logits(std::min(LLMI_SEQ_MAX, B * (lk.draft_len + 1)), true);
+    h2d(lk_samplers_, sp.data(), (size_t)B * sizeof(SamplerDev));
+  }
   // the histories once, each into its own buffer of hist_len + max_new tokens, and the rows' state
   std::vector<int32_t> hbuf(hist_cap, 0);
   std::vector<LookupRow> st((size_t)B);
@@ -671,7 +769,7 @@ void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len
   a.D = D;
   a.ngram_max = lk.ngram_max;
   a.ngram_min = lk.ngram_min;
-  a.argmax = sc_amax_;
+  a.argmax = sampled ? lk_ids_ : sc_amax_;  // the ids the accept compares the drafts with
   a.tok = lk_tok_;
   a.trows = lk_trows_;
   a.blocks = lk_blocks_;
@@ -710,7 +808,8 @@ void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len
         prefill_layers(lk_tok_, T, p0, /*trim=*/false, /*last_chunk=*/false, f16_all, lk_trows_, lk_blocks_, B);
         launch_residual_norm_rows16(pf_out_, E, L_.back().post_ffw_norm, pf_resid_, E, out_norm_, sc_x16_, E, E, T,
                                     hp_.eps, s);
-        launch_score_rows(sa, s);
+        if (!sampled || any_greedy) launch_score_rows(sa, s);
+        if (sampled) lookup_select(lk_trows_, T, W, gather, any_greedy, lk_live_, lk_ids_, lk_snap_, s);
         launch_lookup_step(a, s);
       }
       n_run += g;
@@ -749,6 +848,53 @@ void Session::batch_generate_lookup(const int32_t* hist, const int32_t* hist_len
   lk_last_.trows = lk_ttrows_;
   lk_last_.blocks = lk_tblocks_;
   lk_last_bytes_ = by;
+  if (sampled) {
+    lk_samp_.T = T;
+    lk_samp_.W = W;
+    lk_samp_.gather = gather;
+    lk_samp_.any_greedy = any_greedy;
+  }
+}
+
+// time_kernel(14): the selection of the most recent sampled lookup step -- the live-row list, the logits of the listed
+// rows, soft-cap, select, finalize -- over that step's token rows (lk_snap_), into a list and ids of its own; the
+// final-norm rows are whatever sc_x16_ holds now
+void Session::time_lookup_select(int reps, double* us, double* bytes) {
+  *us = *bytes = 0.0;
+  const int T = lk_samp_.T;
+  if (T == 0 || reps <= 0) return;
+  hipStream_t s = stream_;
+  std::vector<hipEvent_t> ev(2 * (size_t)reps);
+  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+  LLMI_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < reps; r++) {
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+    lookup_select(lk_snap_, T, lk_samp_.W, lk_samp_.gather, lk_samp_.any_greedy, lk_tlive_, lk_tids_, nullptr, s);
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
+  }
+  int32_t n_live = 0;
+  LLMI_HIP(hipMemcpyAsync(&n_live, lk_tlive_ + LLMI_BATCH_TOKENS_MAX, 4, hipMemcpyDeviceToHost, s));
+  LLMI_HIP(hipStreamSynchronize(s));
+  double tot = 0;
+  for (int r = 0; r < reps; r++) {
+    float ms = 0;
+    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
+    tot += ms;
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  *us = tot * 1000.0 / reps;
+  // table reads: one per block of RB listed rows; without the list one per block of every chunk's token rows
+  const int rb = logits_rows_rb(hp_.n_embd);
+  int reads = 0;
+  if (lk_samp_.gather) {
+    reads = (n_live + rb - 1) / rb;
+  } else {
+    for (int c0 = 0; c0 < T; c0 += LLMI_SEQ_MAX) {
+      const int n = std::min(LLMI_SEQ_MAX, T - c0);
+      reads += rb ? (n + rb - 1) / rb : n;
+    }
+  }
+  *bytes = (double)reads * (double)logits_w_.bytes + (double)n_live * vocab_ * 4.0;
 }
 
 // time_kernel(13): lookup_step_kernel's draft search over the most recent lookup call's rows, into tables of its own

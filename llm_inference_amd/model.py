@@ -11,6 +11,7 @@ device session of include/llmi.h.
     last = m.prefill_sequences(prompts, slots)            # prompts straight into their slots
     r = m.batch_extend([chunk, [tok], drafts], [0, 1, 2], [128, 40, 64], out=["none", "last", "all"])  # a ragged step
     r = m.batch_generate_lookup(histories, slots, positions, max_new=64)   # greedy ids, n-gram drafts (section 15)
+    r = m.batch_generate_lookup_sampled(histories, slots, positions, 64, samplers=dict(temperature=0.7, seed=1))  # (16)
 """
 from __future__ import annotations
 
@@ -84,6 +85,16 @@ def normalize_samplers(samplers, B: int):
     if len(sps) != B:
         raise ValueError(f"samplers: {len(sps)} entries for {B} rows")
     return sps
+
+
+def marshal_samplers(sps):
+    """normalize_samplers' list as the ctypes array of llmi_sampler the batch calls take: a None entry (a greedy row)
+    becomes temperature 0, a seed is reduced to 64 bits."""
+    arr = (Sampler * max(len(sps), 1))()
+    for b, sp in enumerate(sps):
+        arr[b] = Sampler(0.0, 0, 1.0, 0) if sp is None else Sampler(sp["temperature"], sp["top_k"], sp["top_p"],
+                                                                   sp["seed"] & 0xFFFFFFFFFFFFFFFF)
+    return arr
 
 
 @dataclass
@@ -413,6 +424,30 @@ class Model:
                                                        ptr(p), B, C.byref(lk), int(max_steps),
                                                        ptr(st) if st.size else None, st.size, ptr(out), ptr(n_out),
                                                        C.byref(stats)))
+        return LookupResult([out[b, :n_out[b]].copy() for b in range(B)], int(stats.steps),
+                            np.array(stats.drafted[:B], np.int32), np.array(stats.accepted[:B], np.int32))
+
+    def batch_generate_lookup_sampled(self, histories, slots: Sequence[int], pos: Sequence[int], max_new: int,
+                                      samplers, draft_len: int = 7, ngram_max: int = 3, ngram_min: int = 1,
+                                      stop: Sequence[int] = (), max_steps: int = 0) -> LookupResult:
+        """llmi_session_batch_generate_lookup_sampled: batch_generate_lookup for sampled rows.
+        samplers as in batch_generate: one dict of set_sampler's keywords for every row, or a sequence of B dicts /
+        None entries (None: a greedy row).  A draft token is accepted when it equals the row's seeded draw at that
+        token's own position, so ids[b] equals row b's ids of batch_generate(first, slots, pos, max_new, stop,
+        samplers=samplers), cut after its stop id -- bit for bit, whatever the histories and draft_len."""
+        tokens, hl, sl, p = marshal_lookup(histories, slots, pos)
+        st = np.ascontiguousarray(stop, np.int32).reshape(-1)
+        B = hl.size
+        if samplers is None:
+            raise ValueError("samplers: None (batch_generate_lookup is the greedy call)")
+        arr = marshal_samplers(normalize_samplers(samplers, B))
+        out = np.full((max(B, 1), max(int(max_new), 1)), -1, np.int32)
+        n_out = np.zeros(max(B, 1), np.int32)
+        lk = Lookup(int(draft_len), int(ngram_max), int(ngram_min), int(max_new))
+        stats = LookupStats()
+        check(lib().llmi_session_batch_generate_lookup_sampled(
+            self.h, ptr(tokens) if tokens.size else None, ptr(hl), ptr(sl), ptr(p), B, C.byref(lk), int(max_steps),
+            ptr(st) if st.size else None, st.size, arr, ptr(out), ptr(n_out), C.byref(stats)))
         return LookupResult([out[b, :n_out[b]].copy() for b in range(B)], int(stats.steps),
                             np.array(stats.drafted[:B], np.int32), np.array(stats.accepted[:B], np.int32))
 

@@ -238,6 +238,47 @@ def logits_rows(x16, w16, softcap: float = 0.0) -> np.ndarray:
     return out
 
 
+def logits_rows_gather(x16, w16, idx, cap: int = 64, softcap: float = 0.0, out=None) -> np.ndarray:
+    """llmi_logits_rows_gather: the gathered multi-row logits GEMV alone.  x16 [T][E], w16
+    [V][E] as logits_rows; idx: at most cap (<= 64) row indices into x16, any order, repeats allowed.  Returns float32
+    [cap][V]: row i < len(idx) carries the bits logits_rows gives row idx[i]; the rows at and past len(idx) are those of
+    `out` (float32 [cap][V], default zeros), which the kernels must not write."""
+    x, w = _f16_bits(x16), _f16_bits(w16)
+    if x.ndim != 2 or w.ndim != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError("logits_rows_gather: x16 [T][E] and w16 [V][E]")
+    T, E = x.shape
+    ix = np.ascontiguousarray(idx, np.int32).reshape(-1)
+    res = np.zeros((max(int(cap), 0), w.shape[0]), np.float32) if out is None else np.array(out, np.float32, order="C")
+    if res.shape != (int(cap), w.shape[0]):
+        raise ValueError("logits_rows_gather: out must be [cap][V]")
+    check(lib().llmi_logits_rows_gather(ptr(x), ptr(w), T, w.shape[0], E, float(softcap), ptr(ix) if ix.size else None,
+                                        ix.size, int(cap), ptr(res)))
+    return res
+
+
+def sample_logits_rows(logits, samplers, sampler_of_row, pos) -> np.ndarray:
+    """llmi_sample_logits_rows: the lookup loop's sampler launches over R <= 512 logits rows [R][V] (DESIGN.md section
+    16).  samplers: dicts of set_sampler's keywords (temperature > 0); row r draws with samplers[sampler_of_row[r]]
+    at position pos[r].  Returns int32 [R]: sample_logits' token per row, -1 for a row with pos < 0."""
+    from ._lib import Sampler
+    lg = np.ascontiguousarray(logits, np.float32)
+    if lg.ndim != 2:
+        raise ValueError("sample_logits_rows: logits [R][V]")
+    R, V = lg.shape
+    of, ps = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (sampler_of_row, pos))
+    if of.size != R or ps.size != R:
+        raise ValueError("sample_logits_rows: one sampler index and one position per row")
+    if R and (of.min() < 0 or of.max() >= len(samplers)):
+        raise ValueError("sample_logits_rows: sampler_of_row names a sampler that was not given")
+    arr = (Sampler * max(len(samplers), 1))()
+    for i, sp in enumerate(samplers):
+        arr[i] = Sampler(float(sp["temperature"]), int(sp.get("top_k", 0)), float(sp.get("top_p", 1.0)),
+                         int(sp.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF)
+    ids = np.zeros(max(R, 1), np.int32)
+    check(lib().llmi_sample_logits_rows(ptr(lg), R, V, arr, ptr(of), ptr(ps), ptr(ids)))
+    return ids[:R]
+
+
 def lookup_draft(history, ngram_max: int = 3, ngram_min: int = 1, draft_len: int = 7):
     """llmi_lookup_draft: the lookup loop's draft rule alone, by its kernel.  The draft is the
     continuation of the most recent earlier occurrence of the history's last n tokens, the longest n in
