@@ -33,10 +33,10 @@ namespace {
 
 // PXF: the fused-exchange variant (tensor-parallel ranks: a.px set; layer_body PXF)
 template <int R, int NW, int P, int E, int ROLE, bool MULTI, bool EARLY, int PE = 0, bool W8 = false, int WT = 0,
-          int RW = 0, bool PXF = false>
+          int RW = 0, bool PXF = false, bool TO = false>
 __global__ __launch_bounds__(NW * 64 + (role_help(ROLE) ? E * 64 : 0)) void gemv_q4_0_layer(LayerGemv a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-  layer_body<R, NW, P, E, ROLE, MULTI, EARLY, 0, PE, W8, WT, RW, PXF>(a, blockIdx.x, s_dyn, BlockSync{});
+  layer_body<R, NW, P, E, ROLE, MULTI, EARLY, 0, PE, W8, WT, RW, PXF, TO>(a, blockIdx.x, s_dyn, BlockSync{});
 }
 
 // K-quant q|k|v of two weight types in one launch (Q4_K_M: q, k Q4_K, v Q6_K):
@@ -65,8 +65,10 @@ __global__ __launch_bounds__(NW * 64) void gemv_kq2_layer(LayerGemv a, LayerGemv
 using LaunchFn = void (*)(dim3, size_t, const LayerGemv&, hipStream_t);
 using Launch2Fn = void (*)(dim3, size_t, const LayerGemv&, const LayerGemv&, int, hipStream_t);
 
+// TO: the tail passes' offsets fixed before the head is issued (layer_body.h tail_offsets); the fused-exchange
+// variant keeps the late offsets
 template <int R, int NW, int P, int E, int ROLE, bool MULTI, bool EARLY, int PE = 0, bool W8 = false, int WT = 0,
-          int RW = 0>
+          int RW = 0, bool TO = false>
 void launch_cfg(dim3 grid, size_t lds, const LayerGemv& a, hipStream_t s) {
   const dim3 block(NW * 64 + (role_help(ROLE) ? E * 64 : 0));
   if (a.px) {  // the fused-exchange variant (tensor-parallel ranks)
@@ -75,12 +77,12 @@ void launch_cfg(dim3 grid, size_t lds, const LayerGemv& a, hipStream_t s) {
   }
   KernelTiming& kt = kernel_timing();
   if (kt.start) {
-    hipExtLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW>), grid, block, (uint32_t)lds,
-                          s, kt.start, kt.stop, 0u, a);
+    hipExtLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW, false, TO>), grid, block,
+                          (uint32_t)lds, s, kt.start, kt.stop, 0u, a);
     kt = KernelTiming{};
     return;
   }
-  hipLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW>), grid, block, lds, s, a);
+  hipLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW, false, TO>), grid, block, lds, s, a);
 }
 
 template <int R, int NW, int P, int E, int ROLE, bool EARLY, int PE, int WTA, int WTB>
@@ -107,6 +109,7 @@ struct LayerCfg {
   Launch2Fn fn2 = nullptr;  // kq: q|k Q4_K + v Q6_K in one launch (PRO / PLAIN qkv entries)
   int rows_max = 0;  // > 0: a tensor-parallel shard entry, for weights of at most this many rows
   int rw = 0;        // > 0: waves carrying rows (layer_body RW), the others only share the prologue
+  LaunchFn fn_late = nullptr;  // TO entries: the instance with the tail offsets left to the compiler (LLMI_FFN_TAIL=late)
 };
 
 #define LLMI_LCFG(NB, ROLE, R, NW, P, E, MULTI, EARLY, SLAB) \
@@ -126,6 +129,11 @@ struct LayerCfg {
 // late roles with the first PE passes issued right after the prologue's loads
 #define LLMI_LCFGP(NB, ROLE, R, NW, P, E, SLAB, PE) \
   {NB, ROLE, R, NW, P, E, false, SLAB, false, launch_cfg<R, NW, P, E, ROLE, false, false, PE>}
+// PE entries whose tail offsets are fixed before the head is issued (TO); fn_late: the instance without
+#define LLMI_LCFGPT(NB, ROLE, R, NW, P, E, SLAB, PE)                                                          \
+  {NB, ROLE, R, NW, P, E, false, SLAB, false,                                                                 \
+   launch_cfg<R, NW, P, E, ROLE, false, false, PE, false, 0, 0, true>, false, 0, nullptr, 0, 0,             \
+   launch_cfg<R, NW, P, E, ROLE, false, false, PE>}
 // Q8_0 weights: row-major, single chunk (P passes of 16-B half blocks)
 // kq entries, one per weight type (+ the q|k Q4_K, v Q6_K launch for qkv roles)
 #define LLMI_LCFGK1(NB, ROLE, R, NW, P, E, EARLY, PE, WT, SLAB)                                        \
@@ -174,7 +182,7 @@ const LayerCfg kLayerCfgs[] = {
     LLMI_LCFG(168, ROLE_PRO, 4, 8, 6, 11, true, true, 0),      // 27B qkv     256 WGs
     // GELU: prologue + GELU epilogue, 2H = R NW interleaved gate/up rows per WG
     LLMI_LCFGP(36, ROLE_GELU, 8, 8, 5, 3, 0, 3),              // 1B  13824 rows, H 32 -> 216 WGs (PE3: 5.9 -> 5.1 us)
-    LLMI_LCFGP(80, ROLE_GELU, 8, 10, 10, 4, 1, 7),            // 4B  20480 rows, H 40 -> 256 WGs (PE7: 8.4 -> 7.8 us)
+    LLMI_LCFGPT(80, ROLE_GELU, 8, 10, 10, 4, 1, 7),           // 4B  20480 rows, H 40 -> 256 WGs (PE7: 8.4 -> 7.8 us)
     LLMI_LCFG(120, ROLE_GELU, 8, 8, 8, 8, true, false, 0),     // 12B 30720 rows, H 32 -> 480 WGs
     // (a 27B gate_up shard entry with longer weight chunks -- P 7 or 11 instead of 4, more bytes in flight per
     // work-group of the tp-8 rank's 84; P does not change a row's pass order: 2.12-2.13 vs 2.08 ms per rank token,
@@ -190,7 +198,7 @@ const LayerCfg kLayerCfgs[] = {
     LLMI_LCFG(216, ROLE_QUANT, 1, 4, 4, 4, false, true, 0),    // 1B down     1152 rows -> 288 WGs (6.5 -> 5.0 us)
     // (a 4B QUANT shard entry, NW 2: 0.948 vs 0.907 ms per tp-8 rank -- 160 work-groups each quantizing the
     // whole 40 KB hid; not kept)
-    LLMI_LCFGP(320, ROLE_QUANT, 1, 10, 5, 2, 0, 3),           // 4B down     2560 rows -> 256 WGs (PE3: 5.8 -> 5.4 us)
+    LLMI_LCFGPT(320, ROLE_QUANT, 1, 10, 5, 2, 0, 3),          // 4B down     2560 rows -> 256 WGs (PE3: 5.8 -> 5.4 us)
     LLMI_LCFG(480, ROLE_QUANT, 1, 8, 8, 4, false, true, 0),    // 12B down    3840 rows -> 480 WGs
     LLMI_LCFG(672, ROLE_QUANT, 1, 8, 6, 6, true, false, 0),    // 27B down    5376 rows -> 672 WGs
     // Q8_0 weights (Gemma-3 1B Q8_0, BASELINE configs[3]): 2 nb half-block units per row
@@ -289,7 +297,10 @@ int launch_layer_gemv(const DevWeight& w, LayerGemv a, int role, hipStream_t s) 
   const int nwg = (w.rows + rows_per_wg - 1) / rows_per_wg;
   if (a.px && a.px_out >= 0 && nwg > PX_MAX_CS) throw std::runtime_error("layer gemv: more fused-exchange producers than checksum slots");
   if (a.px && a.px_in >= 0 && (a.px_in_nwg <= 0 || a.px_in_nwg > PX_MAX_CS)) throw std::runtime_error("layer gemv: fused exchange read without its producer count");
-  c.fn(dim3(nwg), lds, a, s);
+  // LLMI_FFN_TAIL=late: the launch as it was before the tail offsets were fixed early (A/B runs, and the test that
+  // holds the two to the same bits)
+  const char* tail = c.fn_late ? getenv("LLMI_FFN_TAIL") : nullptr;
+  (tail && !strcmp(tail, "late") ? c.fn_late : c.fn)(dim3(nwg), lds, a, s);
   LLMI_HIP(hipGetLastError());
   return nwg;
 }

@@ -110,6 +110,35 @@ __device__ __forceinline__ void load_chunk_rb_part(Chunk<P>& c, __amdgpu_buffer_
   }
 }
 
+// The tail passes [P0, P) with their offsets computed BEFORE the head passes are issued (TO): left to the
+// compiler, the tail's `voq + p sq` became v_mad_u64_u32 whose 64-bit addend's unused high half was a register
+// the head's loads were still to write, so the wave waited for head loads it did not need -- s_waitcnt vmcnt(5)
+// of 14 ahead of the 4B gate_up's x barrier, vmcnt(0) ahead of the 4B down's.  The empty asm pins each offset
+// in a register of its own at that point; the loads and every row's arithmetic are unchanged.
+template <int P, int P0>
+struct TailOff {
+  int q[P - P0 > 0 ? P - P0 : 1], d[P - P0 > 0 ? P - P0 : 1];
+};
+template <int P, int P0>
+__device__ __forceinline__ void tail_offsets(TailOff<P, P0>& o, int voq, int vod, int sq, int sd, int npass) {
+#pragma unroll
+  for (int p = P0; p < P; p++) {
+    const bool in = p < npass;
+    o.q[p - P0] = in ? voq + p * sq : (1 << 30);
+    o.d[p - P0] = in ? vod + p * sd : (1 << 30);
+    asm volatile("" : "+v"(o.q[p - P0]), "+v"(o.d[p - P0]));
+  }
+}
+template <int P, int P0>
+__device__ __forceinline__ void load_chunk_rb_tail(Chunk<P>& c, __amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rd,
+                                                   const TailOff<P, P0>& o) {
+#pragma unroll
+  for (int p = P0; p < P; p++) {
+    c.q[p] = buf_ld16(rq, o.q[p - P0], 0);
+    c.sw[p] = buf_ld2(rd, o.d[p - P0], 0);
+  }
+}
+
 // Q8_0 weights (W8): a lane's 16-B unit is HALF a block (unit u = block
 // u / 2, elements 16 (u % 2) ..; L is even, so the half is lane-fixed: j % 2),
 // dotted with the matching half of the activation block; no zero point
@@ -258,15 +287,30 @@ __device__ __forceinline__ float rb_row_sums(float v, float (&tot)[R <= 2 ? R : 
   return v;
 }
 
-#ifdef LLMI_LAYER_TRACE  // development: per-work-group phase timestamps (scripts/gemv_sweep)
+#ifdef LLMI_LAYER_TRACE  // development: per-work-group phase timestamps (scripts/gemv_sweep, scripts/ffn_trace.py)
+// LAYER_TRACE_W words per work-group, written by thread 0 with plain stores: wall clocks (100 MHz) of
+//   0 start, 1 first weight passes issued, 2 prologue operands landed (QUANT: x quantized), 3 x complete in LDS
+//   (past the barrier), 4 last weight pass issued, 5 last pass consumed, 6 epilogue stores issued, 7 end,
+//   8 / 9 the prologue's first / second reduction done; 10 the wave's HW_ID, 11 its XCC_ID (read once at start)
+constexpr int LAYER_TRACE_W = 16;
 __device__ unsigned long long* g_layer_trace = nullptr;
-#define LAYER_MARK(ph)                                                                                     \
-  do {                                                                                                     \
-    if (g_layer_trace && threadIdx.x == 0) g_layer_trace[(size_t)blockIdx.x * 8 + (ph)] = wall_clock64(); \
+#define LAYER_MARK(ph)                                                                                                 \
+  do {                                                                                                                 \
+    if (g_layer_trace && threadIdx.x == 0) g_layer_trace[(size_t)blockIdx.x * LAYER_TRACE_W + (ph)] = wall_clock64(); \
+  } while (0)
+#define LAYER_MARK_ID()                                                                                     \
+  do {                                                                                                      \
+    if (g_layer_trace && threadIdx.x == 0) {                                                                \
+      g_layer_trace[(size_t)blockIdx.x * LAYER_TRACE_W + 10] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  \
+      g_layer_trace[(size_t)blockIdx.x * LAYER_TRACE_W + 11] = __builtin_amdgcn_s_getreg((31 << 11) | 20); \
+    }                                                                                                       \
   } while (0)
 #else
 #define LAYER_MARK(ph) \
   do {                 \
+  } while (0)
+#define LAYER_MARK_ID() \
+  do {                  \
   } while (0)
 #endif
 
@@ -349,8 +393,9 @@ constexpr int HELP_K4 = 6;  // float4 per helper lane and operand: n <= E * 256 
 // more work-groups for a rank's slice, rows bit-identical to one device's;
 // row-major weights only).
 // PXF: the fused-exchange code (a.px_in / a.px_out honoured); false compiles it out (the one-device launches)
+// TO (PE entries of Q4_0 / Q8_0 weights): the tail passes' offsets are fixed before the head is issued (tail_offsets)
 template <int R, int NW, int P, int E, int ROLE, bool MULTI, bool EARLY, int SYNC = 0, int PE = 0, bool W8 = false,
-          int WT = 0, int RW0 = 0, bool PXF = false>
+          int WT = 0, int RW0 = 0, bool PXF = false, bool TO = false>
 __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, unsigned char* s_dyn,
                                            const BlockSync& bs) {
   constexpr bool HELP = role_help(ROLE);
@@ -363,7 +408,9 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
   static_assert(!W8 || (RB && R <= 16), "W8: row-bound lanes");
   static_assert(WT == 0 || (RB && R <= 8 && !MULTI && !HELP && !W8), "kq: single-chunk row-bound lanes");
   static_assert(!(PXF && HELP), "fused exchange: not in the helper roles (their LDS words are ordered differently)");
+  static_assert(!TO || (PE > 0 && WT == 0), "TO: PE entries, not the kq layout");
   LAYER_MARK(0);
+  LAYER_MARK_ID();
   BLK_MARK(bs, 0);
   constexpr int EPT = E, X_LD = E;
   XBlock* s_x = reinterpret_cast<XBlock*>(s_dyn);
@@ -500,12 +547,15 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
       if constexpr (MULTI) load_chunk<P>(cb, qw, dw, 64 * P, total, lane);
     }
   };
+  TailOff<P, PE> toff;
   auto issue_head = [&]() {  // passes [0, PE)
+    if constexpr (TO) tail_offsets<P, PE>(toff, voq, vod, sq, sd, npass);
     if constexpr (PE > 0 && WT != 0) load_chunk_kq<P, WT, 0, PE>(ca, rq, rd, kq, voq, vod, sq, sd, 0, npass);
     else if constexpr (PE > 0) load_chunk_rb_part<R, P, 0, PE>(ca, rq, rd, voq, vod, sq, sd, npass);
   };
   auto issue_tail = [&]() {  // passes [PE, P), or everything
-    if constexpr (PE > 0 && WT != 0) load_chunk_kq<P, WT, PE, P>(ca, rq, rd, kq, voq, vod, sq, sd, 0, npass);
+    if constexpr (TO) load_chunk_rb_tail<P, PE>(ca, rq, rd, toff);
+    else if constexpr (PE > 0 && WT != 0) load_chunk_kq<P, WT, PE, P>(ca, rq, rd, kq, voq, vod, sq, sd, 0, npass);
     else if constexpr (PE > 0) load_chunk_rb_part<R, P, PE, P>(ca, rq, rd, voq, vod, sq, sd, npass);
     else issue_weights();
   };
@@ -635,6 +685,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
     }
     if constexpr (EARLY) issue_weights();
     else issue_head();
+    LAYER_MARK(1);
     if (yfx) {  // (the weights' first passes are in flight while the peers' words arrive)
 #pragma unroll
       for (int k = 0; k < EB; k++) {
@@ -659,10 +710,10 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
         }
       }
     }
-    LAYER_MARK(1);
+    LAYER_MARK(2);
     BLK_MARK(bs, 5);
     const float sc1 = rms_scale_d(wg_sum<NW>(ss, s_red[0]), n, a.eps);
-    LAYER_MARK(2);
+    LAYER_MARK(8);
     BLK_MARK(bs, 6);
     float ss2 = 0.0f;
 #pragma unroll
@@ -692,7 +743,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
       }
     }
     const float sc2 = rms_scale_d(wg_sum<NW>(ss2, s_red[1]), n, a.eps);
-    LAYER_MARK(3);
+    LAYER_MARK(9);
     BLK_MARK(bs, 7);
 #pragma unroll
     for (int k = 0; k < EB; k++) {
@@ -730,6 +781,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
     }
     if constexpr (EARLY) issue_weights();
     else issue_head();
+    LAYER_MARK(1);
     if (fin) {  // fused exchange: from this rank's mailbox, the weights' first passes in flight
 #pragma unroll
       for (int r = 0; r < E; r++) {
@@ -751,6 +803,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
         }
       }
     }
+    LAYER_MARK(2);
   } else {
     // x blocks -> LDS: clamped unconditional loads (no branch between them
     // and the weight loads, so the stores wait only for their own data)
@@ -800,6 +853,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
   // (HELPER roles: handled above.)
   if constexpr (!HELP) {
     __syncthreads();
+    LAYER_MARK(3);
     if constexpr (!EARLY && SYNC != SYNC_WAIT)
       if (!(ROLE == ROLE_PLAIN && fin)) issue_tail();
   }
@@ -856,6 +910,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
     px_finish();
     if constexpr (SYNC == SYNC_WAIT)
       if (t == 0) block_count_done(bcount, bs.done_n, bs.done, bs.epoch);
+    LAYER_MARK(7);
     return;
   }
   float acc[R];
@@ -897,6 +952,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
   px_finish();
   if constexpr (SYNC == SYNC_WAIT)
     if (t == 0) block_count_done(bcount, bs.done_n, bs.done, bs.epoch);
+  LAYER_MARK(7);
 }
 
 

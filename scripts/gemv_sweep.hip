@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 using namespace llmi;
@@ -215,6 +216,17 @@ int main(int argc, char** argv) {
     qz.out = out;
     if (layer_gemv_supported(probe, LAYER_QUANT))
       timeit("layer quant", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+    // the FFN roles as they were before the tail offsets were fixed early (LLMI_FFN_TAIL=late), same session
+    setenv("LLMI_FFN_TAIL", "late", 1);
+    if (layer_gemv_supported(probe, LAYER_GELU))
+      timeit("layer pro+gelu (tail late)", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
+    if (layer_gemv_supported(probe, LAYER_QUANT))
+      timeit("layer quant (tail late)", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+    unsetenv("LLMI_FFN_TAIL");
+    if (layer_gemv_supported(probe, LAYER_GELU))
+      timeit("layer pro+gelu (again)", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
+    if (layer_gemv_supported(probe, LAYER_QUANT))
+      timeit("layer quant (again)", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
     // MALL experiment: a default-policy prefetch of the same weight right
     // before the GEMV (as a forked graph branch would do during attention)
     {
@@ -231,14 +243,15 @@ int main(int argc, char** argv) {
         timeit("prefetch + layer quant", [&](const DevWeight& w) { pre(w); launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
     }
 #ifdef LLMI_LAYER_TRACE
-    // phase trace of one launch per role (100 MHz ticks, from the first WG start)
+    // phase trace of one launch per role (100 MHz ticks, from the first WG start; slots: layer_body.h LAYER_MARK);
+    // LLMI_FFN_TRACE_DIR: the raw [work-group][LAYER_TRACE_W] words as <dir>/<shape>.<label>.bin (scripts/ffn_trace.py)
     {
+      constexpr int W = LAYER_TRACE_W;
       unsigned long long* tr;
-      const size_t nslot = 4096 * 8;
+      const size_t nslot = 4096 * W;
       LLMI_HIP(hipMalloc(&tr, nslot * 8));
       std::vector<unsigned long long> h(nslot);
       auto trace = [&](const char* label, auto&& launch) {
-        if (!layer_gemv_supported(probe, 0)) {}
         LLMI_HIP(hipMemset(tr, 0, nslot * 8));
         LLMI_HIP(hipStreamSynchronize(s));
         layer_set_trace(tr);
@@ -248,25 +261,37 @@ int main(int argc, char** argv) {
         LLMI_HIP(hipMemcpy(h.data(), tr, nslot * 8, hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull, tend = 0;
         int nwg = 0;
-        double ph[8] = {0};
-        int cnt[8] = {0};
-        for (size_t b = 0; b < nslot / 8; b++) {
-          if (!h[b * 8]) continue;
+        double ph[10] = {0};
+        int cnt[10] = {0};
+        for (size_t b = 0; b < nslot / W; b++) {
+          if (!h[b * W]) continue;
           nwg++;
-          t0 = std::min(t0, h[b * 8]);
+          t0 = std::min(t0, h[b * W]);
         }
-        for (size_t b = 0; b < nslot / 8; b++) {
-          if (!h[b * 8]) continue;
-          for (int k = 0; k < 7; k++)
-            if (h[b * 8 + k]) { ph[k] += (h[b * 8 + k] - t0) / 100.0; cnt[k]++; }
-          tend = std::max(tend, h[b * 8 + 6]);
+        for (size_t b = 0; b < nslot / W; b++) {
+          if (!h[b * W]) continue;
+          for (int k = 0; k < 10; k++)
+            if (h[b * W + k]) { ph[k] += (h[b * W + k] - t0) / 100.0; cnt[k]++; }
+          tend = std::max(tend, h[b * W + 7]);
         }
         printf("%-12s trace %-18s wgs=%d span=%.2f us  mean phase times (us):", sh.name, label, nwg, (tend - t0) / 100.0);
-        for (int k = 0; k < 7; k++) printf(" p%d=%.2f", k, cnt[k] ? ph[k] / cnt[k] : -1.0);
+        for (int k = 0; k < 10; k++) printf(" p%d=%.2f", k, cnt[k] ? ph[k] / cnt[k] : -1.0);
         printf("\n");
+        if (const char* dir = getenv("LLMI_FFN_TRACE_DIR")) {
+          const std::string path = std::string(dir) + "/" + sh.name + "." + label + ".bin";
+          if (FILE* f = fopen(path.c_str(), "wb")) {
+            fwrite(h.data(), 8, (size_t)nwg * W, f);
+            fclose(f);
+          }
+        }
       };
       if (layer_gemv_supported(probe, LAYER_PLAIN)) trace("plain", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_PLAIN), plain, LAYER_PLAIN, s); });
       if (layer_gemv_supported(probe, LAYER_PRO)) trace("pro", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_PRO), pro, LAYER_PRO, s); });
+      // the FFN roles with the tail offsets left to the compiler (the launch before round 13), then as shipped
+      setenv("LLMI_FFN_TAIL", "late", 1);
+      if (layer_gemv_supported(probe, LAYER_GELU)) trace("gelu_late", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
+      if (layer_gemv_supported(probe, LAYER_QUANT)) trace("quant_late", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+      unsetenv("LLMI_FFN_TAIL");
       if (layer_gemv_supported(probe, LAYER_GELU)) trace("gelu", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
       if (layer_gemv_supported(probe, LAYER_QUANT)) trace("quant", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
       (void)hipFree(tr);
@@ -340,6 +365,19 @@ int main(int argc, char** argv) {
     if (nb == 80) {  // 4B gate_up / qkv (x 2560)
       LayerGemv gs = gl, ps = pro;
       gs.slab = ps.slab = 1;
+      // prologue stubbed (timing only, the results are wrong): x copied from pre-quantized blocks, the GELU epilogue
+      // kept -- the bound on what any prologue work can buy
+      {
+        LayerGemv gx = gs;
+        gx.xg = xb;
+        geo_role("SLAB gelu_x R8 NW10 P10 (STUB prologue)", gemv_q4_0_layer<8, 10, 10, 1, ROLE_GELU_X, false, true>, 80, 640, gx, false);
+      }
+      // tail offsets fixed before the head (TO)
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE5 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 5, false, 0, 0, false, true>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE6 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 6, false, 0, 0, false, true>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE8 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 8, false, 0, 0, false, true>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE9 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 9, false, 0, 0, false, true>, 80, 640, gs, true);
       geo_role("gelu R5 NW16 P7 E3 (table, flat)", gemv_q4_0_layer<5, 16, 7, 3, 2, false, false>, 80, 1024, gl, true);
       geo_role("gelu R8 NW10 P10 E4", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false>, 80, 640, gl, true);
       geo_role("gelu R8 NW10 P10 E4 early", gemv_q4_0_layer<8, 10, 10, 4, 2, false, true>, 80, 640, gl, true);
@@ -406,6 +444,12 @@ int main(int argc, char** argv) {
       geo_role("1b quant R2 NW2 P7 E7 (table) b", gemv_q4_0_layer<2, 2, 7, 7, 3, false, true>, 4, 128, qz, false);
     }
     if (nb == 320) {  // 4B down (x 10240)
+      // prologue stubbed (timing only): the PLAIN role at the table's geometry copies pre-quantized blocks
+      geo_role("plain R1 NW10 P5 E2 (STUB prologue)", gemv_q4_0_layer<1, 10, 5, 2, 0, false, true>, 10, 640, plain, false);
+      // tail offsets fixed before the head (TO)
+      geo_role("quant R1 NW10 P5 E2 PE2 TO", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 2, false, 0, 0, false, true>, 10, 640, qz, false);
+      geo_role("quant R1 NW10 P5 E2 PE3 TO", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 3, false, 0, 0, false, true>, 10, 640, qz, false);
+      geo_role("quant R1 NW10 P5 E2 PE4 TO", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 4, false, 0, 0, false, true>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 (table)", gemv_q4_0_layer<1, 10, 5, 2, 3, false, true>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 late", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 PE1", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 1>, 10, 640, qz, false);
