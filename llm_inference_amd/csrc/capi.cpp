@@ -590,8 +590,7 @@ int llmi_sample_logits_rows(const float* logits, int R, int V, const llmi_sample
       } catch (const status_error& e) {
         throw status_error(e.code, std::string("sample_logits_rows: ") + e.what() + " (samplers[" + std::to_string(b) + "])");
       }
-      sp[(size_t)b] = SamplerDev{samplers[b].temperature, samplers[b].top_k == 0 ? LLMI_SAMPLE_MAX_K : samplers[b].top_k,
-                                 samplers[b].top_p, 0, samplers[b].seed};
+      sp[(size_t)b] = sampler_dev(samplers[b]);
     }
     std::vector<SeqRow> rows((size_t)R);
     std::vector<int32_t> list((size_t)R + 1), res((size_t)R, -1);

@@ -8,7 +8,6 @@
 #include "score_plan.h"
 
 #include <cmath>
-#include <functional>
 #include <cstdio>
 #include <cstring>
 
@@ -263,6 +262,7 @@ void Session::upload(const GGUFView& g) {  // model.cpp:169-238 tensor map
     LayerDev& Ld = L_[l];
     Ld.is_swa = l < (int)hp_.swa_layers.size() ? hp_.swa_layers[l] : (l % 6 < 5);  // model.cpp:723-729
     Ld.hd = Ld.is_swa ? hp_.hd_k_swa : hp_.hd_k;
+    max_hd_ = std::max(max_hd_, Ld.hd);
     // shared KV (model.cpp:775-777, 832-835): no K/V projections; the cache of
     // layer kv_from - 2 (SWA) or kv_from - 1 (global) is read instead
     Ld.has_kv = hp_.kv_from < 0 || l < hp_.kv_from;
@@ -447,11 +447,10 @@ void Session::upload(const GGUFView& g) {  // model.cpp:169-238 tensor map
 
 void Session::alloc_buffers() {
   const int E = hp_.n_embd, F = hp_.n_ff;
-  int maxq = 0, maxqkv = 0, maxhd = 0;
+  int maxq = 0, maxqkv = 0;
   for (auto& l : L_) {
     maxq = std::max(maxq, hp_.n_head * l.hd);
     maxqkv = std::max(maxqkv, l.qkv_rows);
-    maxhd = std::max(maxhd, l.hd);
   }
   const int maxcols = std::max({E, F, maxq, vocab_ > 0 ? E : 0});
   resid_ = dalloc<float>(E);
@@ -461,7 +460,7 @@ void Session::alloc_buffers() {
   qkv_ = dalloc<float>(maxqkv);
   q_ = dalloc<float>(maxq);
   attn_ = dalloc<float>(maxq);
-  part_ = dalloc<float>((size_t)hp_.n_head * ATTN_NSPLIT * (maxhd + 2));
+  part_ = dalloc<float>((size_t)hp_.n_head * ATTN_NSPLIT * (max_hd_ + 2));
   ticket_ = dalloc<unsigned>(hp_.n_head);  // per (virtual) kv head, zeroed; the attention kernel resets it after use
   o_out_ = dalloc<float>(E);
   gu_ = dalloc<float>(2 * (size_t)F);
@@ -624,15 +623,12 @@ Session::Session(const uint8_t* gguf, size_t size, const llmi_session_opts& opts
               getenv("LLMI_FULL_LOGITS") == nullptr;
     if (screen_) alloc_screen_table(logits_w_, scr_, stream_);
     if (block_) {
-      int maxrows = 0, maxhd0 = 0;
-      for (const auto& l : L_) {
-        maxrows = std::max(maxrows, l.qkv_rows);
-        maxhd0 = std::max(maxhd0, l.hd);
-      }
+      int maxrows = 0;
+      for (const auto& l : L_) maxrows = std::max(maxrows, l.qkv_rows);
       blk_epoch_ = dalloc<unsigned>(hp_.n_layer);
       blk_done_ = dalloc<unsigned>((size_t)hp_.n_layer * 32);  // (a 128-B line per layer)
       blk_gqkv_stride_ = (size_t)maxrows;
-      blk_gxo_stride_ = (size_t)nh_ * maxhd0 / 32 * 12;
+      blk_gxo_stride_ = (size_t)nh_ * max_hd_ / 32 * 12;
       blk_gqkv_ = dalloc<uint2>((size_t)hp_.n_layer * blk_gqkv_stride_);
       blk_gxo_ = dalloc<uint2>((size_t)hp_.n_layer * blk_gxo_stride_);
       blk_err_ = dalloc<int>(2);
@@ -640,9 +636,7 @@ Session::Session(const uint8_t* gguf, size_t size, const llmi_session_opts& opts
         blk_trace_layer_ = atoi(tr);
         blk_trace_ = dalloc<unsigned long long>(4096 * 8);
       }
-      int maxhd = 0;
-      for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
-      blk_xo_ = dalloc<XBlock>((size_t)nh_ * maxhd / 32 + 1);
+      blk_xo_ = dalloc<XBlock>((size_t)nh_ * max_hd_ / 32 + 1);
     }
     // the batched prefill's chunk buffers for a default-sized prompt now, not inside the first forward (the
     // allocations and their zeroing were ~3 ms of the first 512-token prefill: 14.3 vs 11.0 ms)
@@ -926,10 +920,8 @@ void Session::ensure_prefill_buffers(int cap) {
   pf_x16_ = dalloc<uint16_t>((size_t)cap * pf_xs_ * 32);
   pf_tscale_ = dalloc<float>((size_t)cap);
   pf_q_ = dalloc<uint16_t>((size_t)cap * maxq);
-  int maxhd = 0;
-  for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
   const size_t nqb = (size_t)(cap + 31) / 32;
-  pf_apart_ = dalloc<float>((size_t)nh_ * nqb * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
+  pf_apart_ = dalloc<float>((size_t)nh_ * nqb * PREFILL_ATTN_KS_MAX * 64 * (max_hd_ / 2 + 2));
   if (tp_)  // all-gather staging: the largest exchanged [T][row] activation (f32 rows or Q8_0 block rows)
     pf_gather_ = dalloc<uint8_t>((size_t)cap * std::max({(size_t)E * 4, (size_t)pf_xs_ * sizeof(XBlock), (size_t)pf_xs_ * 64}));
   pf_cap_ = cap;
@@ -1520,10 +1512,8 @@ void Session::setup_xl() {
     d.w[d.n++] = &l.down.w;
     l.xdn = make_xl_weight(d, stream_);
   }
-  int maxhd = 0;
-  for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
   xa_scores_ = dalloc<double>((size_t)hp_.n_head * max_ctx_);
-  xa_xq_ = dalloc<XBlock>((size_t)hp_.n_head * maxhd / 32);
+  xa_xq_ = dalloc<XBlock>((size_t)hp_.n_head * max_hd_ / 32);
   xa_vt_stride_ = (max_ctx_ + 31) / 32 * 32;
   for (auto& l : L_) {  // the tiled V caches (zeroed: columns past the context are loaded, never summed)
     const size_t n = (size_t)hp_.n_head_kv * l.hd * xa_vt_stride_;
@@ -1964,6 +1954,24 @@ void Session::ensure_score_buffers(int cap) {
   sc_cap_ = cap;
 }
 
+ScoreArgs Session::score_args(const uint16_t* x16, int T, const int32_t* targets) const {
+  ScoreArgs a;
+  a.x16 = x16;
+  a.xstride = a.E = hp_.n_embd;
+  a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
+  a.T = T;
+  a.V = vocab_;
+  a.softcap = hp_.final_softcap;
+  a.targets = targets;
+  a.ms = sc_ms_;
+  a.key = sc_key_;
+  a.tl = sc_tl_;
+  a.logprob = sc_lp_;
+  a.lse = sc_lse_;
+  a.argmax = sc_amax_;
+  return a;
+}
+
 // Path 1, one prefill chunk (tokens c0 .. c0 + T of the call): pf_out_ holds the last layer's down rows and
 // pf_resid_ its residual rows for all T tokens.  The final residual + output_norm of every row as f16 -- the image
 // forward(tokens[:i + 1]) hands its logits GEMV -- then the fused scorer over the chunk.
@@ -1977,22 +1985,7 @@ void Session::score_chunk(int c0, int T, hipStream_t s) {
     LLMI_HIP(hipMemcpyAsync(sc_x16_, sc_row0_, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
   LLMI_HIP(hipMemcpyAsync(sc_tgt_, sc_h_tgt_.data() + c0, (size_t)T * 4, hipMemcpyHostToDevice, s));
   tap("sc_x16", -1, sc_x16_, (size_t)T * E * 2, s);
-  ScoreArgs a;
-  a.x16 = sc_x16_;
-  a.xstride = E;
-  a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
-  a.T = T;
-  a.V = vocab_;
-  a.E = E;
-  a.softcap = hp_.final_softcap;
-  a.targets = sc_tgt_;
-  a.ms = sc_ms_;
-  a.key = sc_key_;
-  a.tl = sc_tl_;
-  a.logprob = sc_lp_;
-  a.lse = sc_lse_;
-  a.argmax = sc_amax_;
-  launch_score_rows(a, s);
+  launch_score_rows(score_args(sc_x16_, T, sc_tgt_), s);
   sc_last_T_ = T;
   tap("sc_lse", -1, sc_lse_, (size_t)T * 4, s);
   tap("sc_logprob", -1, sc_lp_, (size_t)T * 4, s);
@@ -2021,13 +2014,8 @@ void Session::score_run(const int32_t* tokens, int n, int pos) {
     }
     set_token_pos(tokens[n - 1], pos + n - 1, true);  // what the token loop leaves behind
     score_mode_ = true;
-    try {
-      prefill(tokens, n, pos);
-    } catch (...) {
-      score_mode_ = sc_row0_set_ = false;
-      throw;
-    }
-    score_mode_ = sc_row0_set_ = false;
+    ScopeExit off{[&] { score_mode_ = sc_row0_set_ = false; }};
+    prefill(tokens, n, pos);
     return;
   }
   // path 2 (and a one-token call, which forward runs as a decode step on every session): the token loop with full
@@ -2325,27 +2313,36 @@ void Session::info(llmi_session_info* o) const {
   o->score_path = score_path();
 }
 
+double Session::time_reps(hipStream_t s, int reps, const std::function<void()>& body) {
+  std::vector<hipEvent_t> ev(2 * (size_t)reps, nullptr);
+  ScopeExit destroy{[&] {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }};
+  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
+  LLMI_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < reps; r++) {
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+    body();
+    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
+  }
+  LLMI_HIP(hipStreamSynchronize(s));
+  double tot = 0;
+  for (int r = 0; r < reps; r++) {
+    float ms = 0;
+    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
+    tot += ms;
+  }
+  return tot;
+}
+
 void Session::time_kernel(int which, int reps, double* us, double* bytes) {
   if (which == 1) {  // F16 logits GEMV (forward's full logits)
     *us = *bytes = 0.0;
     if (reps <= 0) return;
-    std::vector<hipEvent_t> ev(2 * (size_t)reps);
-    for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    for (int r = 0; r < reps; r++) {
-      LLMI_HIP(hipEventRecord(ev[2 * r], stream_));
+    *us = time_reps(stream_, reps, [&] {
       launch_gemv(logits_w_, act_, logits_, exact_ ? GEMV_EXACT : GEMV_FAST, stream_, amax_key_);
-      LLMI_HIP(hipEventRecord(ev[2 * r + 1], stream_));
-    }
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    double tot = 0;
-    for (int r = 0; r < reps; r++) {
-      float ms = 0;
-      LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
-      tot += ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *us = tot * 1000.0 / reps;
+    }) * 1000.0 / reps;
     *bytes = (double)logits_w_.bytes;
     LLMI_HIP(hipMemsetAsync(amax_key_, 0, 8 * (size_t)tp_size_, stream_));
     LLMI_HIP(hipStreamSynchronize(stream_));
@@ -2360,38 +2357,8 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
     *us = *bytes = 0.0;
     if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;
     const int E = hp_.n_embd;
-    ScoreArgs a;
-    a.x16 = sc_x16_;
-    a.xstride = E;
-    a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
-    a.T = sc_last_T_;
-    a.V = vocab_;
-    a.E = E;
-    a.softcap = hp_.final_softcap;
-    a.targets = sc_tgt_;
-    a.ms = sc_ms_;
-    a.key = sc_key_;
-    a.tl = sc_tl_;
-    a.logprob = sc_lp_;
-    a.lse = sc_lse_;
-    a.argmax = sc_amax_;
-    std::vector<hipEvent_t> ev(2 * (size_t)reps);
-    for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    for (int r = 0; r < reps; r++) {
-      LLMI_HIP(hipEventRecord(ev[2 * r], stream_));
-      launch_score_rows(a, stream_);
-      LLMI_HIP(hipEventRecord(ev[2 * r + 1], stream_));
-    }
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    double tot = 0;
-    for (int r = 0; r < reps; r++) {
-      float ms = 0;
-      LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
-      tot += ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *us = tot * 1000.0 / reps;
+    const ScoreArgs a = score_args(sc_x16_, sc_last_T_, sc_tgt_);
+    *us = time_reps(stream_, reps, [&] { launch_score_rows(a, stream_); }) * 1000.0 / reps;
     *bytes = (double)vocab_ * E * 2.0 + (double)sc_last_T_ * E * 2.0;
     return;
   }
@@ -2404,48 +2371,20 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
       sp = d_sampler_ + 1;
       launch_set_sampler(sp, 1.0f, 64, 0.95f, 0ull, stream_);
     }
-    std::vector<hipEvent_t> ev(2 * (size_t)reps);
-    for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    for (int r = 0; r < reps; r++) {
-      LLMI_HIP(hipEventRecord(ev[2 * r], stream_));
+    *us = time_reps(stream_, reps, [&] {
       launch_sample_select(logits_, v_rows_, sp, samp_surv_, stream_);
       launch_sample_finalize(samp_surv_, v_rows_, sp, d_pos_, nullptr, nullptr, nullptr, 0, nullptr, 0,
                              samp_dbg_, stream_);
-      LLMI_HIP(hipEventRecord(ev[2 * r + 1], stream_));
-    }
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    double tot = 0;
-    for (int r = 0; r < reps; r++) {
-      float ms = 0;
-      LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
-      tot += ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *us = tot * 1000.0 / reps;
+    }) * 1000.0 / reps;
     *bytes = (double)v_rows_ * 4.0;
     return;
   }
   if (which == 2) {  // the decode loop's token selection: prep + screening GEMV + rescoring
     *us = *bytes = 0.0;
     if (!screen_ || reps <= 0) return;
-    std::vector<hipEvent_t> ev(2 * (size_t)reps);
-    for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    for (int r = 0; r < reps; r++) {
-      LLMI_HIP(hipEventRecord(ev[2 * r], stream_));
+    *us = time_reps(stream_, reps, [&] {
       launch_screen_argmax(logits_w_, scr_, act_.x16, amax_key_, stream_, false, ex_logits_);
-      LLMI_HIP(hipEventRecord(ev[2 * r + 1], stream_));
-    }
-    LLMI_HIP(hipStreamSynchronize(stream_));
-    double tot = 0;
-    for (int r = 0; r < reps; r++) {
-      float ms = 0;
-      LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * r], ev[2 * r + 1]));
-      tot += ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *us = tot * 1000.0 / reps;
+    }) * 1000.0 / reps;
     *bytes = (double)scr_.bytes;
     LLMI_HIP(hipMemsetAsync(amax_key_, 0, 8 * (size_t)tp_size_, stream_));
     LLMI_HIP(hipStreamSynchronize(stream_));

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <cstdio>
+#include <functional>
 #include <memory>
 #include <string>
 #include <utility>
@@ -23,6 +24,15 @@ struct status_error : std::runtime_error {
 
 // throws LLMI_E_ARG naming the field (temperature < 0 or NaN, top_k outside 0..256, top_p outside (0, 1] or NaN)
 void validate_sampler(const llmi_sampler& sp);
+inline SamplerDev sampler_dev(const llmi_sampler& sp) {  // (validated) top_k 0: no limit but the sampler's own
+  return SamplerDev{sp.temperature, sp.top_k == 0 ? LLMI_SAMPLE_MAX_K : sp.top_k, sp.top_p, 0, sp.seed};
+}
+
+template <class F> struct ScopeExit {  // runs f when the scope ends, by return or by exception
+  F f;
+  ~ScopeExit() { f(); }
+};
+template <class F> ScopeExit(F) -> ScopeExit<F>;
 
 struct HParams {  // model.h:22-43 (Gemma-3 subset)
   std::string arch;
@@ -67,6 +77,15 @@ struct LayerDev {
   float out_scale = 1.0f;        // layer output scale (model.cpp:968-977)
   // the exact-order engine (exact.h): q|k|v, o, gate/up (32-unit interleave), down in the XL layout
   XlWeight xqkv, xo, xgu, xdn;
+};
+
+struct OutRun {  // a step's output rows: token rows row0 .. row0 + n - 1 -> compact rows o0 ..
+  int row0, n, o0;
+  int span, dst;  // (batch_extend: the span they belong to, the caller's entries dst ..)
+};
+struct OutRow0 {  // an output row at position 0: compact output row, bt_row0_ entry (batch_row0)
+  int o, k;
+  bool single;  // its lse / arg-max are that step's too: a batch_step row, a one-token span
 };
 
 class Session {
@@ -228,6 +247,8 @@ class Session {
   XBlock* hq_ = nullptr;         // the GELU launch's Q8_0 blocks of hid (down as a PLAIN launch, 32-unit groups)
   XBlock* blk_xo_ = nullptr;     // attention output Q8_0 blocks (layer 0's qkv still reads act_.q8 in the launch)
   void check_device_error();
+  // time_kernel: reps x (event, body(), event) on s between two synchronises; the summed milliseconds of the pairs
+  static double time_reps(hipStream_t s, int reps, const std::function<void()>& body);
   // a tensor-parallel session whose exchange failed (or that threw between two exchanges) may be out of step with
   // its peers: every later call is refused until the group is re-created
   void ensure_usable() const;
@@ -239,7 +260,8 @@ class Session {
   hipStream_t stream_ = nullptr;
   std::vector<void*> allocs_;
   std::vector<LayerDev> L_;
-  DevWeight embd_;            // token_embd (logits GEMV + embedding rows)
+  int max_hd_ = 0;            // the widest layer's head_dim (upload)
+  DevWeight embd_;           // token_embd (logits GEMV + embedding rows)
   size_t embd_row_bytes_ = 0;
   const uint8_t* embd_raw_ = nullptr;  // GGUF-layout rows for embedding lookups
   float* out_norm_ = nullptr;
@@ -318,6 +340,8 @@ class Session {
   void score_run(const int32_t* tokens, int n, int pos);  // both paths, into sc_h_*
   void score_chunk(int c0, int T, hipStream_t s);         // path 1: the chunk at token offset c0 (inside prefill_run)
   void ensure_score_buffers(int cap);
+  // the fused scorer over T final-norm rows x16 (row stride n_embd), its scratch and results in the sc_* buffers
+  ScoreArgs score_args(const uint16_t* x16, int T, const int32_t* targets) const;
   bool score_mode_ = false;
   bool sc_row0_set_ = false;  // sc_row0_ holds position 0's row as the one-token forward computes it (score_run)
   int sc_cap_ = 0, sc_last_T_ = 0;
@@ -345,11 +369,26 @@ class Session {
   std::vector<SeqRow> bt_last_rows_;       // ... and its rows (host)
   void batch_check(const char* fn, const int32_t* tokens, const int32_t* slots, const int32_t* pos, int B,
                    int n_steps) const;
+  // the argument checks the batch entry points share (f: "<entry point>: "): a slot of the call in range and not
+  // seen before (seen: LLMI_SEQ_MAX flags; span: the slot is a span's), the stop ids into id[0..n_stop), the per-row
+  // samplers as the device's structs
+  void check_slot(const std::string& f, int slot, bool* seen, bool span = false) const;
+  void stop_ids(const std::string& f, const int32_t* stop, int n_stop, int32_t* id) const;
+  struct RowSamplers {
+    std::vector<SamplerDev> dev;
+    bool any_greedy = false, sampled = false;  // some row has temperature 0 / above 0
+  };
+  static RowSamplers row_samplers(const std::string& f, const llmi_sampler* samplers, int B);
   void batch_row0(int32_t token, int slot, int b);  // row b of the step being set up
   // the step's launches for B rows already in bt_tok_ / bt_rows_ (max_pos: the longest row's position; row0: the
   // rows at position 0, whose scorer rows come from bt_row0_); returns whether the f16 path ran
   // score false: the fused scorer's launches are left out (a sampled step none of whose rows is greedy)
-  bool batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0, bool score = true);
+  bool batch_step(int B, int max_pos, bool allow_f16, const std::vector<OutRow0>& row0, bool score = true);
+  // the end of a multi-sequence step, after prefill_layers: the last layer's residual + output norm of each run's rows
+  // as f16 into x16, the position-0 rows from bt_row0_, then (score) the fused scorer over the runs' rows and the
+  // single position-0 rows' lse / arg-max from bt_r0_*
+  void step_tail(uint16_t* x16, const OutRun* runs, size_t n_runs, const std::vector<OutRow0>& r0, bool score);
+  void ensure_batch_apart();  // bt_apart_
   void time_batch_attn(int reps, double* us, double* bytes);
   // the batch loop: greedy (samplers null: batch_generate) or with a sampler per row
   void batch_loop(const char* fn, const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,

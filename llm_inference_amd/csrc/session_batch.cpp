@@ -93,12 +93,43 @@ void Session::batch_check(const char* fn, const int32_t* tokens, const int32_t* 
   bool seen[LLMI_SEQ_MAX] = {};
   for (int b = 0; b < B; b++) {
     if (tokens[b] < 0 || tokens[b] >= vocab_) throw status_error(LLMI_E_RANGE, f + "token id out of range (tokens)");
-    if (slots[b] < 0 || slots[b] >= n_seq_) throw status_error(LLMI_E_RANGE, f + "slot outside [0, n_seq) (slots)");
-    if (seen[slots[b]]) throw status_error(LLMI_E_ARG, f + "duplicate slot in one call (slots)");
-    seen[slots[b]] = true;
+    check_slot(f, slots[b], seen);
     if (pos[b] < 0 || pos[b] + std::max(n_steps, 1) > max_ctx_)
       throw status_error(LLMI_E_RANGE, f + "context overflow (pos + n_steps)");
   }
+}
+
+void Session::check_slot(const std::string& f, int slot, bool* seen, bool span) const {
+  if (slot < 0 || slot >= n_seq_)
+    throw status_error(LLMI_E_RANGE, f + (span ? "slot outside [0, n_seq) (spans.slot)" : "slot outside [0, n_seq) (slots)"));
+  if (seen[slot])
+    throw status_error(LLMI_E_ARG, f + (span ? "duplicate slot in one call (spans.slot)" : "duplicate slot in one call (slots)"));
+  seen[slot] = true;
+}
+
+void Session::stop_ids(const std::string& f, const int32_t* stop, int n_stop, int32_t* id) const {
+  if (n_stop < 0 || n_stop > 4) throw status_error(LLMI_E_ARG, f + "at most 4 stop ids (n_stop)");
+  if (n_stop > 0 && !stop) throw status_error(LLMI_E_ARG, f + "null pointer (stop)");
+  for (int i = 0; id && i < n_stop; i++) {  // (id null: the count and the pointer only)
+    if (stop[i] < 0 || stop[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "stop id out of range (stop)");
+    id[i] = stop[i];
+  }
+}
+
+Session::RowSamplers Session::row_samplers(const std::string& f, const llmi_sampler* samplers, int B) {
+  RowSamplers r;
+  r.dev.resize((size_t)B);
+  for (int b = 0; b < B; b++) {
+    try {
+      validate_sampler(samplers[b]);
+    } catch (const status_error& e) {
+      throw status_error(e.code, f + e.what() + " (samplers[" + std::to_string(b) + "])");
+    }
+    r.dev[(size_t)b] = sampler_dev(samplers[b]);
+    r.any_greedy = r.any_greedy || samplers[b].temperature == 0.0f;
+    r.sampled = r.sampled || samplers[b].temperature > 0.0f;
+  }
+  return r;
 }
 
 // A row at position 0 is a one-token prompt, which forward / score run as a decode step, not as a batched prompt
@@ -112,64 +143,57 @@ void Session::batch_row0(int32_t token, int slot, int b) {
     L_[(size_t)l].kc = bt_h_kvtab_[((size_t)l * LLMI_SEQ_MAX + slot) * 2];
     L_[(size_t)l].vc = bt_h_kvtab_[((size_t)l * LLMI_SEQ_MAX + slot) * 2 + 1];
   }
-  auto restore = [&] {
-    for (int l = 0; l < NL; l++) {
-      L_[(size_t)l].kc = bt_h_kvtab_[(size_t)l * LLMI_SEQ_MAX * 2];
-      L_[(size_t)l].vc = bt_h_kvtab_[(size_t)l * LLMI_SEQ_MAX * 2 + 1];
-    }
-    kernels_per_token_ = kpt;
-  };
-  try {
+  {
+    ScopeExit restore{[&] {
+      for (int l = 0; l < NL; l++) {
+        L_[(size_t)l].kc = bt_h_kvtab_[(size_t)l * LLMI_SEQ_MAX * 2];
+        L_[(size_t)l].vc = bt_h_kvtab_[(size_t)l * LLMI_SEQ_MAX * 2 + 1];
+      }
+      kernels_per_token_ = kpt;
+    }};
     set_token_pos(token, 0, true);
     record_step(stream_, false);  // STEP_LOGITS's launches
     launch_score_reduce_row(logits_, vocab_, -1, bt_r0_lse_ + LLMI_SEQ_MAX + b, bt_r0_lse_ + b, bt_r0_amax_ + b, stream_);
-  } catch (...) {
-    restore();
-    throw;
   }
-  restore();
   LLMI_HIP(hipMemcpyAsync(dst, act_.x16, (size_t)hp_.n_embd * 2, hipMemcpyDeviceToDevice, stream_));
 }
 
-bool Session::batch_step(int B, int max_pos, bool allow_f16, const std::vector<int>& row0, bool score) {
+void Session::ensure_batch_apart() {
+  if (!bt_apart_) bt_apart_ = dalloc<float>((size_t)nh_ * LLMI_SEQ_MAX * PREFILL_ATTN_KS_MAX * 64 * (max_hd_ / 2 + 2));
+}
+
+void Session::step_tail(uint16_t* x16, const OutRun* runs, size_t n_runs, const std::vector<OutRow0>& r0, bool score) {
   hipStream_t s = stream_;
   const int E = hp_.n_embd;
+  int n = 0;
+  for (size_t i = 0; i < n_runs; i++) {
+    const OutRun& o = runs[i];
+    launch_residual_norm_rows16(pf_out_ + (size_t)o.row0 * E, E, L_.back().post_ffw_norm, pf_resid_ + (size_t)o.row0 * E,
+                                E, out_norm_, x16 + (size_t)o.o0 * E, E, E, o.n, hp_.eps, s);
+    n += o.n;
+  }
+  for (const OutRow0& p : r0)
+    LLMI_HIP(hipMemcpyAsync(x16 + (size_t)p.o * E, bt_row0_ + (size_t)p.k * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
+  if (!score) return;
+  launch_score_rows(score_args(x16, n, nullptr), s);
+  for (const OutRow0& p : r0) {  // (batch_row0)
+    if (!p.single) continue;
+    LLMI_HIP(hipMemcpyAsync(sc_lse_ + p.o, bt_r0_lse_ + p.k, 4, hipMemcpyDeviceToDevice, s));
+    LLMI_HIP(hipMemcpyAsync(sc_amax_ + p.o, bt_r0_amax_ + p.k, 4, hipMemcpyDeviceToDevice, s));
+  }
+}
+
+bool Session::batch_step(int B, int max_pos, bool allow_f16, const std::vector<OutRow0>& row0, bool score) {
   ensure_prefill_buffers(B);
   ensure_score_buffers(std::max(B, pf_cap_));
-  if (!bt_apart_) {
-    int maxhd = 0;
-    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
-    bt_apart_ = dalloc<float>((size_t)nh_ * LLMI_SEQ_MAX * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
-  }
+  ensure_batch_apart();
   const bool f16_all = allow_f16 && prefill_f16_ok();
   // prefill_run's chunk with the last layer over every row (LLMI_PREFILL_FULL_LAST's / score's arithmetic); the
   // f16 / int8 GEMM choice per layer is prefill_layers', never a function of B
   prefill_layers(bt_tok_, B, max_pos, /*trim=*/false, /*last_chunk=*/false, f16_all, bt_rows_);
-  launch_residual_norm_rows16(pf_out_, E, L_.back().post_ffw_norm, pf_resid_, E, out_norm_, sc_x16_, E, E, B, hp_.eps, s);
-  for (int b : row0)
-    LLMI_HIP(hipMemcpyAsync(sc_x16_ + (size_t)b * E, bt_row0_ + (size_t)b * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
-  if (!score) return f16_all;
-  ScoreArgs a;
-  a.x16 = sc_x16_;
-  a.xstride = E;
-  a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
-  a.T = B;
-  a.V = vocab_;
-  a.E = E;
-  a.softcap = hp_.final_softcap;
-  a.targets = nullptr;
-  a.ms = sc_ms_;
-  a.key = sc_key_;
-  a.tl = sc_tl_;
-  a.logprob = sc_lp_;
-  a.lse = sc_lse_;
-  a.argmax = sc_amax_;
-  launch_score_rows(a, s);
-  for (int b : row0) {  // (batch_row0)
-    LLMI_HIP(hipMemcpyAsync(sc_lse_ + b, bt_r0_lse_ + b, 4, hipMemcpyDeviceToDevice, s));
-    LLMI_HIP(hipMemcpyAsync(sc_amax_ + b, bt_r0_amax_ + b, 4, hipMemcpyDeviceToDevice, s));
-  }
-  sc_last_T_ = B;
+  const OutRun all{0, B, 0, 0, 0};
+  step_tail(sc_x16_, &all, 1, row0, score);
+  if (score) sc_last_T_ = B;
   return f16_all;
 }
 
@@ -185,7 +209,7 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
     const int n = (int)idx.size();
     std::vector<SeqRow> rows((size_t)n);
     std::vector<int32_t> tok((size_t)n);
-    std::vector<int> row0;
+    std::vector<OutRow0> row0;
     int max_pos = 0;
     for (int i = 0; i < n; i++) {
       rows[(size_t)i] = SeqRow{slots[idx[(size_t)i]], pos[idx[(size_t)i]]};
@@ -193,7 +217,7 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
       max_pos = std::max(max_pos, rows[(size_t)i].pos);
       if (rows[(size_t)i].pos == 0) {
         batch_row0(tok[(size_t)i], rows[(size_t)i].slot, i);
-        row0.push_back(i);
+        row0.push_back(OutRow0{i, i, true});
       }
     }
     h2d(bt_rows_, rows.data(), (size_t)n * sizeof(SeqRow));
@@ -257,20 +281,14 @@ void Session::launch_batch_attn(const PrefillAttn& at, int T, hipStream_t s) {
 void Session::ensure_extend_buffers() {
   const int E = hp_.n_embd;
   if (!bx_rows_) {
-    int maxhd = 0;
-    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
     const size_t max_blocks = LLMI_SEQ_MAX + LLMI_BATCH_TOKENS_MAX / 32;
     bx_rows_ = dalloc<SeqRow>(LLMI_BATCH_TOKENS_MAX);
     bx_tok_ = dalloc<int32_t>(LLMI_BATCH_TOKENS_MAX);
     bx_blocks_ = dalloc<AttnBlock>(max_blocks);
-    bx_apart_ = dalloc<float>((size_t)nh_ * max_blocks * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
+    bx_apart_ = dalloc<float>((size_t)nh_ * max_blocks * PREFILL_ATTN_KS_MAX * 64 * (max_hd_ / 2 + 2));
     bx_x16_ = dalloc<uint16_t>((size_t)LLMI_BATCH_TOKENS_MAX * E);
   }
-  if (!bt_apart_) {  // (the per-token form's partials, as batch_step)
-    int maxhd = 0;
-    for (const auto& l : L_) maxhd = std::max(maxhd, l.hd);
-    bt_apart_ = dalloc<float>((size_t)nh_ * LLMI_SEQ_MAX * PREFILL_ATTN_KS_MAX * 64 * (maxhd / 2 + 2));
-  }
+  ensure_batch_apart();  // (the per-token form's partials, as batch_step)
 }
 
 // A ragged batch step: the batched prefill's launch sequence over the spans' token rows -- the
@@ -287,9 +305,7 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
   std::vector<int> tok_off((size_t)n_spans), out_off((size_t)n_spans);
   for (int i = 0; i < n_spans; i++) {
     const llmi_span& sp = spans[i];
-    if (sp.slot < 0 || sp.slot >= n_seq_) throw status_error(LLMI_E_RANGE, f + "slot outside [0, n_seq) (spans.slot)");
-    if (seen[sp.slot]) throw status_error(LLMI_E_ARG, f + "duplicate slot in one call (spans.slot)");
-    seen[sp.slot] = true;
+    check_slot(f, sp.slot, seen, /*span=*/true);
     if (sp.n_tokens < 1) throw status_error(LLMI_E_ARG, f + "a span needs at least one token (spans.n_tokens)");
     if (sp.out < LLMI_SPAN_LAST || sp.out > LLMI_SPAN_NONE)
       throw status_error(LLMI_E_ARG, f + "out must be LLMI_SPAN_LAST, _ALL or _NONE (spans.out)");
@@ -320,15 +336,8 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
     std::vector<SeqRow> rows;
     std::vector<int32_t> tok;
     std::vector<AttnBlock> blocks;
-    struct Run {  // a span's output rows: token rows row0 .. row0 + n - 1 -> compact rows o0 .., caller's entries dst ..
-      int span, row0, n, o0, dst;
-    };
-    std::vector<Run> outs;
-    struct Row0 {  // an output row at position 0: compact output row, bt_row0_ entry, a one-token span
-      int o, k;
-      bool single;
-    };
-    std::vector<Row0> r0;
+    std::vector<OutRun> outs;  // a span's output rows
+    std::vector<OutRow0> r0;   // (single: a one-token span)
     int max_pos = 0, n_out = 0;
     for (int k = 0; k < (int)idx.size(); k++) {
       const llmi_span& sp = spans[idx[(size_t)k]];
@@ -343,14 +352,14 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
       max_pos = std::max(max_pos, sp.pos + sp.n_tokens - 1);
       if (sp.out == LLMI_SPAN_NONE) continue;
       const int n = sp.out == LLMI_SPAN_ALL ? sp.n_tokens : 1;
-      outs.push_back(Run{idx[(size_t)k], t0 + sp.n_tokens - n, n, n_out, out_off[(size_t)idx[(size_t)k]]});
+      outs.push_back(OutRun{t0 + sp.n_tokens - n, n, n_out, idx[(size_t)k], out_off[(size_t)idx[(size_t)k]]});
       // an output row at position 0 is forward's / score's one-token step (batch_row0); the step below then rewrites
       // the slot's K / V row 0 with the batched prefill's bits.  As score() does it: a one-token span's lse / arg-max
       // are that step's (the f64 row reduce, score's one-token call); a longer span hands the step's final-norm row
       // to the fused scorer with its other rows (score_chunk's sc_row0_)
       if (sp.pos + sp.n_tokens - n == 0) {
         batch_row0(st[0], sp.slot, k);
-        r0.push_back(Row0{n_out, k, sp.n_tokens == 1});
+        r0.push_back(OutRow0{n_out, k, sp.n_tokens == 1});
       }
       n_out += n;
     }
@@ -363,15 +372,12 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
     h2d(bx_blocks_, blocks.data(), blocks.size() * sizeof(AttnBlock));
     ensure_prefill_buffers(T);
     const bool f16_all = allow_f16 && prefill_f16_ok();
-    bx_step_ = true;
-    try {  // the last layer over every row, as batch_step
+    {  // the last layer over every row, as batch_step
+      bx_step_ = true;
+      ScopeExit off{[&] { bx_step_ = false; }};
       prefill_layers(bx_tok_, T, max_pos, /*trim=*/false, /*last_chunk=*/false, f16_all, bx_rows_,
                      span_rows ? nullptr : bx_blocks_, span_rows ? 0 : (int)blocks.size());
-    } catch (...) {
-      bx_step_ = false;
-      throw;
     }
-    bx_step_ = false;
     bx_last_rows_ = rows;
     bx_last_blocks_ = blocks;
     if (n_out == 0) {  // no final norm, no scorer, no GEMV (and no f16 check, like batch_generate)
@@ -380,34 +386,8 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
       return false;
     }
     ensure_score_buffers(std::max(n_out, pf_cap_));
-    // the output rows' final-norm rows, compact in span order
-    for (const Run& o : outs)
-      launch_residual_norm_rows16(pf_out_ + (size_t)o.row0 * E, E, L_.back().post_ffw_norm, pf_resid_ + (size_t)o.row0 * E,
-                                  E, out_norm_, bx_x16_ + (size_t)o.o0 * E, E, E, o.n, hp_.eps, s);
-    for (const Row0& p : r0)
-      LLMI_HIP(hipMemcpyAsync(bx_x16_ + (size_t)p.o * E, bt_row0_ + (size_t)p.k * E, (size_t)E * 2,
-                              hipMemcpyDeviceToDevice, s));
-    ScoreArgs a;
-    a.x16 = bx_x16_;
-    a.xstride = E;
-    a.w16 = static_cast<const uint16_t*>(logits_w_.qs);
-    a.T = n_out;
-    a.V = vocab_;
-    a.E = E;
-    a.softcap = hp_.final_softcap;
-    a.targets = nullptr;
-    a.ms = sc_ms_;
-    a.key = sc_key_;
-    a.tl = sc_tl_;
-    a.logprob = sc_lp_;
-    a.lse = sc_lse_;
-    a.argmax = sc_amax_;
-    launch_score_rows(a, s);
-    for (const Row0& p : r0) {  // (batch_row0)
-      if (!p.single) continue;
-      LLMI_HIP(hipMemcpyAsync(sc_lse_ + p.o, bt_r0_lse_ + p.k, 4, hipMemcpyDeviceToDevice, s));
-      LLMI_HIP(hipMemcpyAsync(sc_amax_ + p.o, bt_r0_amax_ + p.k, 4, hipMemcpyDeviceToDevice, s));
-    }
+    // the output rows' final-norm rows, compact in span order, and the scorer over them
+    step_tail(bx_x16_, outs.data(), outs.size(), r0, /*score=*/true);
     hx.resize((size_t)n_out * E);
     std::vector<int32_t> am((size_t)n_out);
     std::vector<float> ls((size_t)n_out);
@@ -416,7 +396,7 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
     LLMI_HIP(hipMemcpyAsync(ls.data(), sc_lse_, (size_t)n_out * 4, hipMemcpyDeviceToHost, s));
     if (logits) {  // forward's logits GEMV on the compact rows, LLMI_SEQ_MAX of them at a time (bt_logits_'s size)
       ensure_batch_logits(std::min(n_out, LLMI_SEQ_MAX), false);
-      for (const Run& o : outs)
+      for (const OutRun& o : outs)
         for (int c0 = 0; c0 < o.n; c0 += LLMI_SEQ_MAX) {
           const int n = std::min(LLMI_SEQ_MAX, o.n - c0);
           batch_logits(n, s, bx_x16_ + (size_t)(o.o0 + c0) * E);
@@ -426,13 +406,13 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
     }
     LLMI_HIP(hipStreamSynchronize(s));
     check_device_error();
-    for (const Run& o : outs)
+    for (const OutRun& o : outs)
       for (int j = 0; j < o.n; j++) {
         if (argmax) argmax[o.dst + j] = am[(size_t)(o.o0 + j)];
         if (lse) lse[o.dst + j] = ls[(size_t)(o.o0 + j)];
       }
     bad.clear();
-    for (const Run& o : outs)
+    for (const OutRun& o : outs)
       for (size_t i = (size_t)o.o0 * E; i < (size_t)(o.o0 + o.n) * E; i++)
         if (!f16_finite(hx[i])) {
           bad.push_back(o.span);
@@ -492,28 +472,12 @@ void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* sl
                          int n_steps, const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out) {
   const std::string f = std::string(fn) + ": ";
   batch_check(fn, first, slots, pos, B, n_steps);
-  if (n_stop < 0 || n_stop > 4) throw status_error(LLMI_E_ARG, f + "at most 4 stop ids (n_stop)");
-  if (n_stop > 0 && !stop) throw status_error(LLMI_E_ARG, f + "null pointer (stop)");
   BatchStops st{};
   st.n = n_stop;
-  for (int i = 0; i < n_stop; i++) {
-    if (stop[i] < 0 || stop[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "stop id out of range (stop)");
-    st.id[i] = stop[i];
-  }
-  std::vector<SamplerDev> sp;
-  bool any_greedy = false;
+  stop_ids(f, stop, n_stop, st.id);
+  RowSamplers sp;
   if (samplers) {
-    sp.resize((size_t)B);
-    for (int b = 0; b < B; b++) {
-      try {
-        validate_sampler(samplers[b]);
-      } catch (const status_error& e) {
-        throw status_error(e.code, f + e.what() + " (samplers[" + std::to_string(b) + "])");
-      }
-      sp[(size_t)b] = SamplerDev{samplers[b].temperature, samplers[b].top_k == 0 ? LLMI_SAMPLE_MAX_K : samplers[b].top_k,
-                                 samplers[b].top_p, 0, samplers[b].seed};
-      any_greedy = any_greedy || samplers[b].temperature == 0.0f;
-    }
+    sp = row_samplers(f, samplers, B);
     int ept = 0;
     if (sample_groups(vocab_, &ept) == 0) throw status_error(LLMI_E_ARG, f + "vocabulary over 1,048,576 rows");
   }
@@ -527,17 +491,18 @@ void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* sl
   if (samplers) {
     if (!bt_samplers_) bt_samplers_ = dalloc<SamplerDev>(LLMI_SEQ_MAX);
     ensure_batch_logits(B, true);
-    h2d(bt_samplers_, sp.data(), (size_t)B * sizeof(SamplerDev));
+    h2d(bt_samplers_, sp.dev.data(), (size_t)B * sizeof(SamplerDev));
   }
   std::vector<SeqRow> rows((size_t)B);
-  std::vector<int> row0;
+  std::vector<OutRow0> row0;
+  const std::vector<OutRow0> none;
   int max_pos = 0;
   for (int b = 0; b < B; b++) {
     rows[(size_t)b] = SeqRow{slots[b], pos[b]};
     max_pos = std::max(max_pos, pos[b]);
     if (pos[b] == 0) {
       batch_row0(first[b], slots[b], b);
-      row0.push_back(b);
+      row0.push_back(OutRow0{b, b, true});
     }
   }
   h2d(bt_rows_, rows.data(), (size_t)B * sizeof(SeqRow));
@@ -545,7 +510,7 @@ void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* sl
   // every step's launches are enqueued at once: tokens, positions, the ids and the stop flags stay on the device
   // (max_pos + i bounds the longest live row: it only decides whether the attention's merge is launched)
   for (int i = 0; i < n_steps; i++) {
-    batch_step(B, max_pos + i, true, i == 0 ? row0 : std::vector<int>(), !samplers || any_greedy);
+    batch_step(B, max_pos + i, true, i == 0 ? row0 : none, !samplers || sp.any_greedy);
     if (i + 1 == n_steps)  // time_kernel(10) / (11): the last step's rows as it ran them (pos -1: ended before it)
       LLMI_HIP(hipMemcpyAsync(rows.data(), bt_rows_, (size_t)B * sizeof(SeqRow), hipMemcpyDeviceToHost, s));
     if (!samplers) {
@@ -639,8 +604,7 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
   if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
   if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
   if (B < 1 || B > n_seq_) throw status_error(LLMI_E_RANGE, f + "B must be in 1..n_seq (B)");
-  if (n_stop < 0 || n_stop > 4) throw status_error(LLMI_E_ARG, f + "at most 4 stop ids (n_stop)");
-  if (n_stop > 0 && !stop) throw status_error(LLMI_E_ARG, f + "null pointer (stop)");
+  stop_ids(f, stop, n_stop, nullptr);  // (the ids' range is checked where it always was, below)
   if (lk.draft_len < 1 || lk.draft_len > LOOKUP_DRAFT_MAX)
     throw status_error(LLMI_E_RANGE, f + "draft_len must be in 1..31 (draft_len)");
   if (lk.ngram_max < 1 || lk.ngram_max > LOOKUP_NGRAM_MAX)
@@ -654,18 +618,13 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
   if (max_steps < 0) throw status_error(LLMI_E_ARG, f + "negative step count (max_steps)");
   LookupArgs a;
   a.n_stop = n_stop;
-  for (int i = 0; i < n_stop; i++) {
-    if (stop[i] < 0 || stop[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "stop id out of range (stop)");
-    a.stop[i] = stop[i];
-  }
-  const int D = lk.draft_len, W = D + 1, T = B * W, max_new = lk.max_new, E = hp_.n_embd;
+  stop_ids(f, stop, n_stop, a.stop);
+  const int D = lk.draft_len, W = D + 1, T = B * W, max_new = lk.max_new;
   bool seen[LLMI_SEQ_MAX] = {};
   size_t n_hist = 0, hist_cap = 0;
   int p0 = 0;
   for (int b = 0; b < B; b++) {
-    if (slots[b] < 0 || slots[b] >= n_seq_) throw status_error(LLMI_E_RANGE, f + "slot outside [0, n_seq) (slots)");
-    if (seen[slots[b]]) throw status_error(LLMI_E_ARG, f + "duplicate slot in one call (slots)");
-    seen[slots[b]] = true;
+    check_slot(f, slots[b], seen);
     if (hist_len[b] < 1) throw status_error(LLMI_E_RANGE, f + "a history needs at least one token (hist_len)");
     // a position-0 row is a one-token prompt, which forward / score run as a decode step (batch_row0): batch_generate
     // runs it before its loop, a lookup step would need it inside
@@ -679,25 +638,14 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
   }
   for (size_t i = 0; i < n_hist; i++)
     if (hist[i] < 0 || hist[i] >= vocab_) throw status_error(LLMI_E_RANGE, f + "token id out of range (hist)");
-  std::vector<SamplerDev> sp;
-  bool any_greedy = false, sampled = false;
+  RowSamplers sp;
   if (samplers) {
-    sp.resize((size_t)B);
-    for (int b = 0; b < B; b++) {
-      try {
-        validate_sampler(samplers[b]);
-      } catch (const status_error& e) {
-        throw status_error(e.code, f + e.what() + " (samplers[" + std::to_string(b) + "])");
-      }
-      sp[(size_t)b] = SamplerDev{samplers[b].temperature, samplers[b].top_k == 0 ? LLMI_SAMPLE_MAX_K : samplers[b].top_k,
-                                 samplers[b].top_p, 0, samplers[b].seed};
-      any_greedy = any_greedy || samplers[b].temperature == 0.0f;
-      sampled = sampled || samplers[b].temperature > 0.0f;
-    }
+    sp = row_samplers(f, samplers, B);
     int ept = 0;  // (only a row that draws needs the sampler: all-greedy samplers are the greedy call)
-    if (sampled && sample_groups(vocab_, &ept) == 0)
+    if (sp.sampled && sample_groups(vocab_, &ept) == 0)
       throw status_error(LLMI_E_ARG, f + "vocabulary over 1,048,576 rows");
   }
+  const bool any_greedy = sp.any_greedy, sampled = sp.sampled;
   // (samplers that are all greedy: the greedy loop's launches, nothing else)
   // A/B, read at the call: the logits of every token row, without the list (also the table widths the multi-row
   // GEMV does not take, through batch_logits' row-by-row path)
@@ -739,7 +687,7 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
     }
     lk_samp_.T = 0;
     ensure_batch_logits(std::min(LLMI_SEQ_MAX, B * (lk.draft_len + 1)), true);
-    h2d(lk_samplers_, sp.data(), (size_t)B * sizeof(SamplerDev));
+    h2d(lk_samplers_, sp.dev.data(), (size_t)B * sizeof(SamplerDev));
   }
   // the histories once, each into its own buffer of hist_len + max_new tokens, and the rows' state
   std::vector<int32_t> hbuf(hist_cap, 0);
@@ -779,36 +727,25 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
   a.mode = LOOKUP_DRAFT;  // the first step's draft and tables
   launch_lookup_step(a, s);
   a.mode = LOOKUP_STEP;
-  ScoreArgs sa;
-  sa.x16 = sc_x16_;
-  sa.xstride = E;
-  sa.w16 = static_cast<const uint16_t*>(logits_w_.qs);
-  sa.T = T;
-  sa.V = vocab_;
-  sa.E = E;
-  sa.softcap = hp_.final_softcap;
-  sa.targets = nullptr;
-  sa.ms = sc_ms_;
-  sa.key = sc_key_;
-  sa.tl = sc_tl_;
-  sa.logprob = sc_lp_;
-  sa.lse = sc_lse_;
-  sa.argmax = sc_amax_;
+  const OutRun all{0, T, 0, 0, 0};
+  const std::vector<OutRow0> none;  // (no row starts at position 0)
   const bool f16_all = prefill_f16_ok();
-  // the span attention's launches are recorded for time_kernel(12), which times batch_extend's steps: kept as they were
-  const std::vector<PrefillAttn> keep_attn = bx_last_attn_;
   std::vector<int32_t> flags((size_t)B, 0);
-  bx_step_ = true;
-  try {
+  {
+    // the span attention's launches are recorded for time_kernel(12), which times batch_extend's steps: kept as they were
+    std::vector<PrefillAttn> keep_attn = bx_last_attn_;
+    bx_step_ = true;
+    ScopeExit off{[&] {
+      bx_step_ = false;
+      bx_last_attn_ = std::move(keep_attn);
+    }};
     bool all_done = false;
     for (int n_run = 0; n_run < cap_steps && !all_done;) {
       const int g = std::min(group, cap_steps - n_run);
       for (int i = 0; i < g; i++) {
         // p0: the last position any row may reach, a bound for the attention's merge launch (as batch_loop's)
         prefill_layers(lk_tok_, T, p0, /*trim=*/false, /*last_chunk=*/false, f16_all, lk_trows_, lk_blocks_, B);
-        launch_residual_norm_rows16(pf_out_, E, L_.back().post_ffw_norm, pf_resid_, E, out_norm_, sc_x16_, E, E, T,
-                                    hp_.eps, s);
-        if (!sampled || any_greedy) launch_score_rows(sa, s);
+        step_tail(sc_x16_, &all, 1, none, /*score=*/!sampled || any_greedy);
         if (sampled) lookup_select(lk_trows_, T, W, gather, any_greedy, lk_live_, lk_ids_, lk_snap_, s);
         launch_lookup_step(a, s);
       }
@@ -818,13 +755,7 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
       all_done = true;
       for (int b = 0; b < B; b++) all_done = all_done && flags[(size_t)b] != 0;
     }
-  } catch (...) {
-    bx_step_ = false;
-    bx_last_attn_ = keep_attn;
-    throw;
   }
-  bx_step_ = false;
-  bx_last_attn_ = keep_attn;
   sc_last_T_ = T;
   LLMI_HIP(hipMemcpyAsync(st.data(), lk_rowst_, (size_t)B * sizeof(LookupRow), hipMemcpyDeviceToHost, s));
   LLMI_HIP(hipMemcpyAsync(out, lk_out_, (size_t)B * max_new * 4, hipMemcpyDeviceToHost, s));
@@ -864,25 +795,12 @@ void Session::time_lookup_select(int reps, double* us, double* bytes) {
   const int T = lk_samp_.T;
   if (T == 0 || reps <= 0) return;
   hipStream_t s = stream_;
-  std::vector<hipEvent_t> ev(2 * (size_t)reps);
-  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-  LLMI_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < reps; r++) {
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+  *us = time_reps(s, reps, [&] {
     lookup_select(lk_snap_, T, lk_samp_.W, lk_samp_.gather, lk_samp_.any_greedy, lk_tlive_, lk_tids_, nullptr, s);
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
-  }
-  int32_t n_live = 0;
+  }) * 1000.0 / reps;
+  int32_t n_live = 0;  // (as the timed launches left it)
   LLMI_HIP(hipMemcpyAsync(&n_live, lk_tlive_ + LLMI_BATCH_TOKENS_MAX, 4, hipMemcpyDeviceToHost, s));
   LLMI_HIP(hipStreamSynchronize(s));
-  double tot = 0;
-  for (int r = 0; r < reps; r++) {
-    float ms = 0;
-    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
-    tot += ms;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *us = tot * 1000.0 / reps;
   // table reads: one per block of RB listed rows; without the list one per block of every chunk's token rows
   const int rb = logits_rows_rb(hp_.n_embd);
   int reads = 0;
@@ -902,23 +820,7 @@ void Session::time_lookup_step(int reps, double* us, double* bytes) {
   *us = *bytes = 0.0;
   if (lk_last_.B == 0 || reps <= 0) return;
   hipStream_t s = stream_;
-  std::vector<hipEvent_t> ev(2 * (size_t)reps);
-  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-  LLMI_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < reps; r++) {
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
-    launch_lookup_step(lk_last_, s);
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
-  }
-  LLMI_HIP(hipStreamSynchronize(s));
-  double tot = 0;
-  for (int r = 0; r < reps; r++) {
-    float ms = 0;
-    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
-    tot += ms;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *us = tot * 1000.0 / reps;
+  *us = time_reps(s, reps, [&] { launch_lookup_step(lk_last_, s); }) * 1000.0 / reps;
   *bytes = lk_last_bytes_;
 }
 
@@ -932,25 +834,11 @@ void Session::time_batch_sampling(int reps, double* us, double* bytes) {
   h2d(bt_trows_, bt_samp_rows_.data(), (size_t)B * sizeof(SeqRow));
   const int rb = logits_rows_rb(E);
   const BatchStops st{};
-  std::vector<hipEvent_t> ev(2 * (size_t)reps);
-  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-  LLMI_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < reps; r++) {
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+  *us = time_reps(s, reps, [&] {
     batch_logits(B, s);
     launch_sample_select_rows(bt_logits_, vocab_, B, bt_samplers_, bt_trows_, bt_surv_, s);
     launch_sample_finalize_rows(bt_surv_, vocab_, B, bt_samplers_, sc_amax_, bt_trows_, bt_tok_, st, bt_ring_, false, s);
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
-  }
-  LLMI_HIP(hipStreamSynchronize(s));
-  double tot = 0;
-  for (int r = 0; r < reps; r++) {
-    float ms = 0;
-    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
-    tot += ms;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *us = tot * 1000.0 / reps;
+  }) * 1000.0 / reps;
   const int reads = rb ? (B + rb - 1) / rb : B;
   *bytes = (double)reads * (double)logits_w_.bytes + (double)B * vocab_ * 4.0;
 }
@@ -966,28 +854,14 @@ void Session::time_batch_attn(int reps, double* us, double* bytes) {
   for (const auto& r : bt_last_rows_) max_pos = std::max(max_pos, r.pos);
   for (int l = 0; l < NL; l++)
     for (const auto& r : bt_last_rows_) by += r.pos < 0 ? 0.0 : (double)(r.pos + 1) * 2.0 * nkv_ * L_[(size_t)l].hd * 2.0;
-  std::vector<hipEvent_t> ev(2 * (size_t)reps);
-  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-  LLMI_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < reps; r++) {
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+  *us = time_reps(s, reps, [&] {
     for (int l = 0; l < NL; l++) {  // the launches write only the step's scratch rows (the o projection's x)
       PrefillAttn at = bt_last_attn_[(size_t)l];
       at.rows = bt_trows_;
       at.pos0 = max_pos;
       launch_prefill_attn(at, B, s);
     }
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
-  }
-  LLMI_HIP(hipStreamSynchronize(s));
-  double tot = 0;
-  for (int r = 0; r < reps; r++) {
-    float ms = 0;
-    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
-    tot += ms;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *us = tot * 1000.0 / reps / NL;
+  }) * 1000.0 / reps / NL;
   *bytes = by / NL;
 }
 
@@ -1004,23 +878,9 @@ void Session::time_extend_attn(int reps, double* us, double* bytes) {
   double by = 0.0;  // K and V rows 0 .. last position of every query block, once per block
   for (int l = 0; l < NL; l++)
     for (const auto& b : bx_last_blocks_) by += (double)(b.pos + b.n) * 2.0 * nkv_ * L_[(size_t)l].hd * 2.0;
-  std::vector<hipEvent_t> ev(2 * (size_t)reps);
-  for (auto& e : ev) LLMI_HIP(hipEventCreate(&e));
-  LLMI_HIP(hipStreamSynchronize(s));
-  for (int r = 0; r < reps; r++) {
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r], s));
+  *us = time_reps(s, reps, [&] {
     for (int l = 0; l < NL; l++) launch_batch_attn(bx_last_attn_[(size_t)l], T, s);  // (writes the o projection's x only)
-    LLMI_HIP(hipEventRecord(ev[2 * (size_t)r + 1], s));
-  }
-  LLMI_HIP(hipStreamSynchronize(s));
-  double tot = 0;
-  for (int r = 0; r < reps; r++) {
-    float ms = 0;
-    LLMI_HIP(hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]));
-    tot += ms;
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *us = tot * 1000.0 / reps / NL;
+  }) * 1000.0 / reps / NL;
   *bytes = by / NL;
 }
 
