@@ -411,6 +411,22 @@ int llmi_lookup_draft(const int32_t* hist, int L, int ngram_max, int ngram_min, 
 int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits);
 int llmi_logits_rows_rb(int E);
 
+/* op level, host pointers, synchronous: out[t][n] = tscale[t] * sum_k f16(d (q - 8))[n][k] x16[t][k], the f16 x Q4_0
+ * GEMM of the batch steps and the f16 prefill.  w_blocks: Q4_0 blocks in GGUF form
+ * [n_rows][n_cols / 32][18 B]; x16: [T][n_cols] f16 bits; tscale: [T] or NULL (1); out: [T][ostride] f32, ostride >=
+ * n_rows -- only out[t][0 .. n_rows) of the T rows is written.  kernel: 0 = the session's choice
+ * (llmi_gemm_rows_plan), 1 = the skinny kernel (T <= 64), 2 = the tiled kernel (v6); 1 and 2 write the same bits.
+ * slab: 1 = the weight is repacked slab-major as the session's layer weights are (n_cols % 256 == 0).
+ * Errors: NULL pointers, kernel outside 0..2, slab outside 0..1: LLMI_E_ARG; T outside 1..LLMI_BATCH_TOKENS_MAX, or
+ * kernel 1 with T > 64: LLMI_E_RANGE; n_rows % 64 != 0, n_cols % 128 != 0, slab with n_cols % 256 != 0, ostride <
+ * n_rows: LLMI_E_SIZE. */
+int llmi_gemm_rows_f16(const void* w_blocks, int n_rows, int n_cols, const uint16_t* x16, int T, const float* tscale,
+                       int kernel, int slab, float* out, int ostride);
+/* no GPU work: the kernel llmi_gemm_rows_f16(kernel = 0) and the session run for a Q4_0 weight [n_rows][n_cols] at T
+ * token rows: 1 = skinny (T <= 8, where it measured faster), 6 or 7 = the tiled kernels v6 / v7; 0: the shape is
+ * not supported.  (LLMI_PG_SKINNY=0: never 1.) */
+int llmi_gemm_rows_plan(int n_rows, int n_cols, int T);
+
 /* Enqueue n_steps decode steps without waiting (bench); llmi_session_sync
  * waits and copies the produced tokens (may be NULL). */
 int llmi_session_enqueue(llmi_session* s, int32_t first, int pos, int n_steps);
@@ -508,7 +524,11 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *       logits (after a call under LLMI_LOOKUP_NO_GATHER=1: one read per block of every chunk's token rows, and all
  *       B (draft_len + 1) rows' logits); 0 / 0 before any such step.
  * Returns the mean microseconds and the mean algorithmic bytes per launch
- * (0 / 0 when the family does not exist on this session). */
+ * (0 / 0 when the family does not exist on this session).  *  15 = the four projections' GEMM launches (qkv, o, gate_up, down) of every layer as the most recent batch / extend /
+ *       lookup step made them, at that step's token-row count and on its activation buffers, one pass over the layers
+ *       per repetition (the weights come from HBM); us per layer, bytes = one layer's weights (0 / 0 before any such
+ *       step, and on tensor-parallel sessions).
+ */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);
 
 /* Device self-tests of arithmetic the exact kernels rely on (synchronous, current device):

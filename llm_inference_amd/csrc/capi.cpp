@@ -684,6 +684,51 @@ int llmi_lookup_draft(const int32_t* hist, int L, int ngram_max, int ngram_min, 
 
 int llmi_logits_rows_rb(int E) { return logits_rows_rb(E); }
 
+int llmi_gemm_rows_plan(int n_rows, int n_cols, int T) {
+  if (n_rows <= 0 || n_cols <= 0 || n_cols % 32 || T < 1) return 0;
+  return prefill_gemm16_plan(n_rows, n_cols, 0, T);
+}
+
+int llmi_gemm_rows_f16(const void* w_blocks, int n_rows, int n_cols, const uint16_t* x16, int T, const float* tscale,
+                       int kernel, int slab, float* out, int ostride) {
+  return guard([&] {
+    if (!w_blocks || !x16 || !out) throw status_error(LLMI_E_ARG, "gemm_rows_f16: null pointer");
+    if (kernel < 0 || kernel > 2) throw status_error(LLMI_E_ARG, "gemm_rows_f16: kernel must be 0, 1 or 2 (kernel)");
+    if (slab < 0 || slab > 1) throw status_error(LLMI_E_ARG, "gemm_rows_f16: slab must be 0 or 1 (slab)");
+    if (T < 1 || T > LLMI_BATCH_TOKENS_MAX)
+      throw status_error(LLMI_E_RANGE, "gemm_rows_f16: T must be in 1.." + std::to_string(LLMI_BATCH_TOKENS_MAX) + " (T)");
+    if (kernel == 1 && T > GEMM_ROWS_T_MAX)
+      throw status_error(LLMI_E_RANGE, "gemm_rows_f16: the skinny kernel takes T <= " + std::to_string(GEMM_ROWS_T_MAX) + " (T)");
+    if (n_rows <= 0 || n_rows % 64 || n_cols <= 0 || n_cols % 128)
+      throw status_error(LLMI_E_SIZE, "gemm_rows_f16: n_rows must be a multiple of 64, n_cols of 128");
+    if (slab && n_cols % 256) throw status_error(LLMI_E_SIZE, "gemm_rows_f16: the slab layout needs n_cols % 256 == 0");
+    if (ostride < n_rows) throw status_error(LLMI_E_SIZE, "gemm_rows_f16: ostride < n_rows");
+    Ctx& c = ctx();
+    DevWeight w = alloc_weight(T_Q4_0, n_rows, n_cols);
+    try {
+      upload_rows(w, 0, w_blocks, n_rows, c.stream);
+      if (slab) to_slab_layout(w, c.stream);
+      if (!prefill_gemm16_supported(w)) throw status_error(LLMI_E_SIZE, "gemm_rows_f16: unsupported shape");
+      const size_t xb = (size_t)T * n_cols * 2, ob = (size_t)T * ostride * 4;
+      uint16_t* xd = (uint16_t*)c.get(0, xb);
+      float* od = (float*)c.get(1, ob);
+      float* td = (float*)c.get(2, (size_t)T * 4);
+      LLMI_HIP(hipMemcpyAsync(xd, x16, xb, hipMemcpyHostToDevice, c.stream));
+      LLMI_HIP(hipMemcpyAsync(od, out, ob, hipMemcpyHostToDevice, c.stream));  // (what the launch does not write stays)
+      if (tscale) LLMI_HIP(hipMemcpyAsync(td, tscale, (size_t)T * 4, hipMemcpyHostToDevice, c.stream));
+      launch_prefill_gemm16(w, xd, n_cols, T, od, ostride, tscale ? td : nullptr, c.stream,
+                            kernel == 1 ? 1 : kernel == 2 ? 6 : 0);
+      LLMI_HIP(hipMemcpyAsync(out, od, ob, hipMemcpyDeviceToHost, c.stream));
+      LLMI_HIP(hipStreamSynchronize(c.stream));
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      free_weight(w);
+      throw;
+    }
+    free_weight(w);
+  });
+}
+
 int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits) {
   return guard([&] {
     if (!x16 || !w16 || !logits) throw status_error(LLMI_E_ARG, "logits_rows: null pointer");

@@ -1976,18 +1976,36 @@ static bool launch_gemm7(const PrefillGemm16& a, bool wide, hipStream_t s) {
   return wide ? try_gemm7<2, 2, 2, 2>(a, s) : try_gemm7<1, 2, 2, 2>(a, s);
 }
 
+// The kernel launch_prefill_gemm16 runs for a Q4_0 weight: 7, 6 or 1 = the skinny kernel (k_gemm_rows.hip), which
+// takes v6's launches at T <= GEMM_ROWS_T_SKINNY and computes v6's bits (LLMI_PG_SKINNY=0: v6 itself, for A/B); 0: none.
+// Q4_0: v7 with 128 x 128 tiles where they fill the chip twice over (gate_up: 640 work-groups at T = 512), v6
+// elsewhere (its K split over wave groups keeps 256-320 work-groups of 8 waves busy where v7 has 80-128).
+// In-model, 4B 512-token prefill (scripts/dev/pfprof_geo.sh): 9.76 ms this way, 9.97 with v7 64 x 128 tiles
+// for qkv / o (which scripts/dev/pg7_bench -- 20 launches of one GEMM, weights warm in the Infinity Cache --
+// has ahead), 10.2 with v6 everywhere, 10.9-11.2 with the int8 v5
+int prefill_gemm16_plan(int rows, int cols, int slab, int T) {
+  DevWeight w;
+  w.type = T_Q4_0;
+  w.rows = rows;
+  w.cols = cols;
+  w.slab = slab;
+  const bool wide = (rows / 128) * ((T + 127) / 128) >= 512;
+  const bool v6 = getenv("LLMI_PG6") || (!getenv("LLMI_PG7") && !wide && prefill_gemm16_supported(w));
+  if (prefill_gemm7_supported(w) && !v6) return 7;
+  if (!prefill_gemm16_supported(w)) return 0;
+  const char* sk = getenv("LLMI_PG_SKINNY");
+  const bool skinny = T <= GEMM_ROWS_T_SKINNY && !wide && !getenv("LLMI_PG7") && !getenv("LLMI_PG6_GEO") && !(sk && atoi(sk) == 0);
+  return skinny ? 1 : 6;
+}
+
 // v6 geometry: the K split depends on K alone (tensor-parallel shards
 // sum in the same order as the whole weight)
 void launch_prefill_gemm16(const DevWeight& w, const uint16_t* x, int xstride, int T, float* out, int ostride,
-                           const float* tscale, hipStream_t s) {
-  // Q4_0: v7 with 128 x 128 tiles where they fill the chip twice over (gate_up: 640 work-groups at T = 512), v6
-  // elsewhere (its K split over wave groups keeps 256-320 work-groups of 8 waves busy where v7 has 80-128).
-  // In-model, 4B 512-token prefill (scripts/dev/pfprof_geo.sh): 9.76 ms this way, 9.97 with v7 64 x 128 tiles
-  // for qkv / o (which scripts/dev/pg7_bench -- 20 launches of one GEMM, weights warm in the Infinity Cache --
-  // has ahead), 10.2 with v6 everywhere, 10.9-11.2 with the int8 v5
+                           const float* tscale, hipStream_t s, int force) {
   const bool wide = (w.rows / 128) * ((T + 127) / 128) >= 512;
-  const bool v6 = getenv("LLMI_PG6") || (!getenv("LLMI_PG7") && !wide && prefill_gemm16_supported(w));
-  if (prefill_gemm7_supported(w) && !v6) {
+  const int plan = force ? force : w.type == T_Q4_0 ? prefill_gemm16_plan(w.rows, w.cols, w.slab, T) : 6;
+  if (plan == 1 && !gemm_rows_supported(w)) throw std::runtime_error("gemm_rows: unsupported weight");
+  if (plan == 7 || plan == 1) {
     PrefillGemm16 a;
     a.qs = reinterpret_cast<const uint4*>(w.qs);
     a.wd = w.d;
@@ -2000,6 +2018,7 @@ void launch_prefill_gemm16(const DevWeight& w, const uint16_t* x, int xstride, i
     a.out = out;
     a.ostride = ostride;
     a.tscale = tscale;
+    if (plan == 1) return launch_gemm_rows(a, s);
     if (!launch_gemm7(a, wide, s)) throw std::runtime_error("prefill_gemm16: shape outside the v7 geometries");
     LLMI_HIP(hipGetLastError());
     return;

@@ -1066,6 +1066,10 @@ void Session::prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, 
     else gather_cols(pf_xq_ + (size_t)t0 * XS, (size_t)XS * sizeof(XBlock), (size_t)(cols / 32) * sizeof(XBlock), T_cur_, s);
   };
   T_cur_ = T;
+  if (rows || blocks) {  // time_kernel(15): the most recent batch / extend / lookup step's row count
+    gr_last_T_ = T;
+    gr_last_f16_ = f16_all;
+  }
   PrefillNorm en;
   en.table = embd_raw_;
   en.emb_type = embd_.type;
@@ -2336,6 +2340,42 @@ double Session::time_reps(hipStream_t s, int reps, const std::function<void()>& 
   return tot;
 }
 
+// time_kernel(15): the four projections' GEMM launches of every layer as prefill_layers makes them at the row count
+// of the most recent batch / extend / lookup step, on that step's activation buffers (the outputs go to pf_out_,
+// which the next step overwrites).  One pass over the layers per repetition: the weights rotate through all of the
+// model's layers, so they come from HBM and not from the Infinity Cache.
+void Session::time_gemm_rows(int reps, double* us, double* bytes) {
+  *us = *bytes = 0.0;
+  if (tp_ || gr_last_T_ <= 0 || reps <= 0 || !pf_x16_) return;
+  const int T = gr_last_T_, E = hp_.n_embd, XS = pf_xs_, X16 = pf_xs_ * 32;
+  hipStream_t s = stream_;
+  bool f16 = gr_last_f16_;
+  auto gemm = [&](const DevWeight& w, float* out, int ostride, bool scaled) {
+    if (f16) launch_prefill_gemm16(w, pf_x16_, X16, T, out, ostride, scaled ? pf_tscale_ : nullptr, s);
+    else launch_prefill_gemm(w, pf_xq_, XS, T, out, ostride, s);
+  };
+  // LLMI_GR_ONLY=0..3: one projection alone (qkv, o, gate_up, down; scripts/bench_gemm_rows.py)
+  const char* oe = getenv("LLMI_GR_ONLY");
+  const int only = oe ? atoi(oe) : -1;
+  auto on = [&](int k) { return only < 0 || only == k; };
+  *us = time_reps(s, reps, [&] {
+    for (int l = 0; l < hp_.n_layer; l++) {
+      const LayerDev& Ld = L_[l];
+      f16 = gr_last_f16_;
+      for (size_t pi = 0, r0 = 0; on(0) && pi < Ld.qkv.size(); r0 += Ld.qkv[pi].w.rows, pi++)
+        gemm(Ld.qkv[pi].w, pf_out_ + r0, Ld.qkv_rows, true);
+      if (l + 1 == hp_.n_layer && !pf_kq_) f16 = false;  // (the last layer's int8 detour)
+      if (on(1)) gemm(Ld.o.w, pf_out_, E, false);
+      if (on(2)) gemm(Ld.gate_up[0].w, pf_out_, 2 * hp_.n_ff, true);
+      if (on(3)) gemm(Ld.down.w, pf_out_, E, true);
+    }
+  }) * 1000.0 / reps / hp_.n_layer;
+  const LayerDev& L0 = L_[0];
+  for (const auto& q : L0.qkv) *bytes += on(0) ? (double)q.w.bytes : 0.0;
+  *bytes += (on(1) ? (double)L0.o.w.bytes : 0.0) + (on(2) ? (double)L0.gate_up[0].w.bytes : 0.0) +
+            (on(3) ? (double)L0.down.w.bytes : 0.0);
+}
+
 void Session::time_kernel(int which, int reps, double* us, double* bytes) {
   if (which == 1) {  // F16 logits GEMV (forward's full logits)
     *us = *bytes = 0.0;
@@ -2353,6 +2393,7 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
   if (which == 12) return time_extend_attn(reps, us, bytes);
   if (which == 13) return time_lookup_step(reps, us, bytes);
   if (which == 14) return time_lookup_select(reps, us, bytes);
+  if (which == 15) return time_gemm_rows(reps, us, bytes);
   if (which == 9) {  // the fused scorer's two launches over the most recently scored chunk (its rows are still there)
     *us = *bytes = 0.0;
     if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;

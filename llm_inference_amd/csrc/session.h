@@ -130,6 +130,7 @@ class Session {
   void set_sampler(const llmi_sampler* sp);  // null or temperature 0: greedy
   void info(llmi_session_info* out) const;
   void time_kernel(int which, int reps, double* us, double* bytes);
+  void time_gemm_rows(int reps, double* us, double* bytes);  // time_kernel(15)
   void peer_handle(void* out) const;
   void peer_connect(const void* handles);
 
@@ -401,6 +402,8 @@ class Session {
   float* bt_logits_ = nullptr;                // [bt_logits_cap_][vocab] grow-only
   unsigned long long* bt_surv_ = nullptr;     // [bt_logits_cap_][SAMPLE_MAX_GROUPS x 256]
   int bt_logits_cap_ = 0, bt_surv_cap_ = 0;
+  int gr_last_T_ = 0;                         // token rows of the most recent batch / extend / lookup step (time_kernel(15))
+  bool gr_last_f16_ = false;                  // ... and whether it ran the f16 GEMMs
   int bt_samp_B_ = 0;                         // rows of the most recent sampled batch step (time_kernel(11))
   std::vector<SeqRow> bt_samp_rows_;          // ... as it ran them
   void ensure_batch_logits(int B, bool surv);

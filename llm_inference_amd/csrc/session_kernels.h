@@ -231,8 +231,20 @@ void launch_prefill_gemm(const DevWeight& w, const XBlock* x, int xstride, int T
 // (the default prefill GEMM where prefill_gemm7_supported), v6 for the K-quants
 bool prefill_gemm16_supported(const DevWeight& w);
 bool prefill_gemm7_supported(const DevWeight& w);
+// force: 0 the plan below, 1 the skinny kernel, 6 v6 (the op-level entry's choice)
 void launch_prefill_gemm16(const DevWeight& w, const uint16_t* x, int xstride, int T, float* out, int ostride,
-                           const float* tscale, hipStream_t s);
+                           const float* tscale, hipStream_t s, int force = 0);
+// The kernel launch_prefill_gemm16 runs for a Q4_0 weight [rows][cols] at T token rows: 7, 6, or 1 = the skinny
+// kernel below; 0: the shape is outside prefill_gemm16_supported.  No GPU work.
+int prefill_gemm16_plan(int rows, int cols, int slab, int T);
+// The skinny GEMM (k_gemm_rows.hip): v6's bits for 1 <= T <= GEMM_ROWS_T_MAX rows of f16
+// activations times a Q4_0 weight within prefill_gemm16_supported, weights streamed global -> registers
+constexpr int GEMM_ROWS_T_MAX = 64;
+// the rows up to which launch_prefill_gemm16 picks it: measured faster than v6 at 1 and 8 rows, slower at 32 and 64
+// (DESIGN.md section 17.4), not measured between
+constexpr int GEMM_ROWS_T_SKINNY = 8;
+bool gemm_rows_supported(const DevWeight& w);
+void launch_gemm_rows(const PrefillGemm16& a, hipStream_t s);
 void launch_prefill_qk(const PrefillQK& a, int T, hipStream_t s);
 void launch_prefill_attn(const PrefillAttn& a, int T, hipStream_t s);
 void launch_prefill_gelu(const float* gu, int F, int H, XBlock* xq, int xstride, int T, hipStream_t s,

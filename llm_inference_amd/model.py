@@ -473,6 +473,10 @@ class Model:
         check(lib().llmi_session_peer_connect(self.h, b))
 
     def time_kernel(self, which: int, reps: int):
+        """llmi_session_time_kernel: (us per launch, bytes per launch) of kernel family `which` (include/llmi.h lists
+        them).  15: the four projections' GEMM launches of every layer as the most recent batch / extend / lookup
+        step made them, at that step's row count -- us per layer and one layer's weight bytes; 0 / 0 before any such
+        step."""
         us, by = C.c_double(), C.c_double()
         check(lib().llmi_session_time_kernel(self.h, which, reps, C.byref(us), C.byref(by)))
         return us.value, by.value

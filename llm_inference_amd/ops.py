@@ -224,6 +224,40 @@ def logits_rows_rb(E: int) -> int:
     return int(lib().llmi_logits_rows_rb(int(E)))
 
 
+def gemm_rows_plan(n_rows: int, n_cols: int, T: int) -> int:
+    """llmi_gemm_rows_plan: the kernel gemm_rows(kernel="auto") and the session run for a Q4_0 weight [n_rows][n_cols]
+    at T token rows -- 1 the skinny kernel, 6 / 7 the tiled ones, 0 unsupported.  No GPU work."""
+    return int(lib().llmi_gemm_rows_plan(int(n_rows), int(n_cols), int(T)))
+
+
+_GEMM_ROWS_KERNELS = {"auto": 0, "skinny": 1, "tiled": 2}
+
+
+def gemm_rows(w_blocks, n_rows: int, n_cols: int, x16, tscale=None, kernel: str = "auto", slab: bool = False,
+              out=None) -> np.ndarray:
+    """llmi_gemm_rows_f16: the f16 x Q4_0 GEMM of the batch steps alone.  w_blocks: the Q4_0
+    blocks in GGUF form (uint8, n_rows x n_cols / 32 x 18 B); x16 [T][n_cols] float16 (or its uint16 bits); tscale
+    [T] float32 or None.  kernel: "auto" (gemm_rows_plan), "skinny" (T <= 64) or "tiled" (v6) -- the last two write
+    the same bits.  slab: repack the weight slab-major as the session does.  Returns float32 [T][ostride]: `out`
+    (default zeros [T][n_rows]) with [t][0 .. n_rows) of every row overwritten and nothing else."""
+    wb = np.ascontiguousarray(w_blocks).view(np.uint8).reshape(-1)
+    x = _f16_bits(x16)
+    if kernel not in _GEMM_ROWS_KERNELS:
+        raise ValueError("gemm_rows: kernel must be 'auto', 'skinny' or 'tiled'")
+    if x.ndim != 2 or x.shape[1] != n_cols or wb.size != n_rows * (n_cols // 32) * 18:
+        raise ValueError("gemm_rows: x16 [T][n_cols] and n_rows x n_cols / 32 Q4_0 blocks")
+    T = x.shape[0]
+    ts = None if tscale is None else np.ascontiguousarray(tscale, np.float32).reshape(-1)
+    if ts is not None and ts.size != T:
+        raise ValueError("gemm_rows: one tscale per row")
+    res = np.zeros((T, n_rows), np.float32) if out is None else np.array(out, np.float32, order="C")
+    if res.ndim != 2 or res.shape[0] != T:
+        raise ValueError("gemm_rows: out must be [T][ostride]")
+    check(lib().llmi_gemm_rows_f16(ptr(wb), int(n_rows), int(n_cols), ptr(x), T, ptr(ts) if ts is not None else None,
+                                   _GEMM_ROWS_KERNELS[kernel], int(bool(slab)), ptr(res), res.shape[1]))
+    return res
+
+
 def logits_rows(x16, w16, softcap: float = 0.0) -> np.ndarray:
     """llmi_logits_rows: the multi-row F16 logits GEMV alone.  x16 [T][E] and w16 [V][E] as
     float16 (or their uint16 bits); returns float32 [T][V] whose row t carries the bits of the fast F16
