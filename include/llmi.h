@@ -174,6 +174,19 @@ int llmi_session_forward(llmi_session* s, const int32_t* tokens, int n_tokens, i
  * (llmi_session_info.score_path). */
 int llmi_session_score(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const int32_t* targets,
                        float* logprob, float* lse, int32_t* argmax);
+/* The same call, and beside it the top_n most likely ids of every position with their log-probs (the top_logprobs of
+ * completion APIs): top_ids / top_logprobs are [n_tokens][top_n], both required.
+ * For finite logits, top_ids[i] are the top_n largest of the scorer's own f32 logits of position i, descending by
+ * value, ties by lower id, and top_logprobs[i][j] = (float)((double)logit - lse_i) with lse_i before its rounding:
+ * top_ids[i][0] == argmax[i]; where top_ids[i][j] == targets[i], top_logprobs[i][j] is logprob[i] bit for bit; nothing
+ * depends on n_tokens, the chunking or the other tokens of the call.  logprob / lse / argmax are llmi_session_score's
+ * bits.  The fused path rescores top_n vocabulary tiles per token from the scorer's tile keys (the logits are still
+ * never written); the row path selects from each full logits row.
+ * 1 <= top_n <= min(LLMI_SCORE_TOP_MAX, vocabulary), else LLMI_E_RANGE; tensor-parallel session: LLMI_E_ARG. */
+#define LLMI_SCORE_TOP_MAX 32
+int llmi_session_score_top(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const int32_t* targets,
+                           float* logprob, float* lse, int32_t* argmax, int top_n, int32_t* top_ids,
+                           float* top_logprobs);
 
 /* Several sequences per step.  Fast sessions on one device with a batched prefill, the fused
  * scorer (F16 output table), Gemma-3 layers of Q4_0 / Q8_0 weights (no K-quant layers) and head_dim 128 or 256 only;
@@ -236,6 +249,11 @@ int llmi_session_batch_extend(llmi_session* s, const int32_t* tokens, const llmi
  * (row-major), softcap <= 0: none.  E % 16 == 0, else LLMI_E_SIZE. */
 int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
                     const int32_t* targets, float* logprob, float* lse, int32_t* argmax);
+/* and with the top-N pass: top_ids / top_logprobs [T][top_n] as llmi_session_score_top's,
+ * 1 <= top_n <= min(LLMI_SCORE_TOP_MAX, V), else LLMI_E_RANGE. */
+int llmi_score_rows_top(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                        const int32_t* targets, float* logprob, float* lse, int32_t* argmax, int top_n,
+                        int32_t* top_ids, float* top_logprobs);
 
 /* Layer-by-layer triage: llmi_session_forward's token
  * loop, one token at a time with eager launches, appending the

@@ -124,6 +124,7 @@ _SIGS = {
     "llmi_session_peer_connect": (C.c_int, [_vp, _vp]),
     "llmi_session_forward": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "llmi_session_score": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "llmi_session_score_top": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     "llmi_session_seq_reserve": (C.c_int, [_vp, C.c_int]),
     "llmi_session_seq_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "llmi_session_batch_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
@@ -145,6 +146,8 @@ _SIGS = {
     "llmi_gemm_rows_f16": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "llmi_gemm_rows_plan": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "llmi_score_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),
+    "llmi_score_rows_top": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp, C.c_int, _vp,
+                                      _vp]),
     "llmi_session_generate": (C.c_int, [_vp, _i32, C.c_int, C.c_int, _vp]),
     "llmi_session_dump": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_char_p]),
     "llmi_session_enqueue": (C.c_int, [_vp, _i32, C.c_int, C.c_int]),

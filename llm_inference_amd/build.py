@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libllmi.so")
-SOURCES = ["k_gemv.hip", "k_layer.hip", "k_elem.hip", "k_attn.hip", "k_session.hip", "k_prefill.hip", "k_gemm_rows.hip", "k_logits.hip", "k_exchange.hip", "k_exact.hip", "k_sample.hip", "k_score.hip", "k_lookup.hip", "session.cpp", "session_batch.cpp", "collective.cpp", "capi.cpp"]
+SOURCES = ["k_gemv.hip", "k_layer.hip", "k_elem.hip", "k_attn.hip", "k_session.hip", "k_prefill.hip", "k_gemm_rows.hip", "k_logits.hip", "k_exchange.hip", "k_exact.hip", "k_sample.hip", "k_score.hip", "k_score_top.hip", "k_lookup.hip", "session.cpp", "session_batch.cpp", "collective.cpp", "capi.cpp"]
 HEADERS = ["common.h", "kernels.h", "attn.h", "layer_body.h", "session_kernels.h", "session.h", "gguf_reader.h", "collective.h",
            "exact.h", "px.h", "glibc_math.h", "spec_chain.h", "sample.h", "score_plan.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -40,9 +40,12 @@ def _mtime(p):
 
 
 # per-file flags: the prefill GEMM's epilogue FMAs stay scalar (packed f32 beside MFMAs costs more issue
-# cycles than two v_fmac_f32, MI355X_MICROARCH 'price of one filler beside MFMAs')
+# cycles than two v_fmac_f32, MI355X_MICROARCH 'price of one filler beside MFMAs'); the kernels added since
+# (k_gemm_rows.hip, k_score_top.hip) are built with the packed f32 instructions (v_pk_*_f32) off altogether --
+# a scalar and a packed f32 operation round alike, so k_score_top.hip's soft-cap gives k_score.hip's bits
 FILE_FLAGS = {"k_prefill.hip": ["-fno-slp-vectorize"],
-              "k_gemm_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "k_gemm_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "k_score_top.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _compile(src: str) -> str:

@@ -441,6 +441,17 @@ int llmi_session_score(llmi_session* s, const int32_t* tokens, int n_tokens, int
   });
 }
 
+int llmi_session_score_top(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const int32_t* targets,
+                           float* logprob, float* lse, int32_t* argmax, int top_n, int32_t* top_ids,
+                           float* top_logprobs) {
+  return guard([&] {
+    if (!s || (!tokens && n_tokens > 0)) throw status_error(LLMI_E_ARG, "score_top: null pointer");
+    if (top_n < 1) throw status_error(LLMI_E_RANGE, "score_top: top_n outside 1 .. min(LLMI_SCORE_TOP_MAX, vocabulary) (top_n)");
+    if (!top_ids || !top_logprobs) throw status_error(LLMI_E_ARG, "score_top: null pointer (top_ids / top_logprobs)");
+    s->s->score(tokens, n_tokens, pos, targets, logprob, lse, argmax, top_n, top_ids, top_logprobs);
+  });
+}
+
 int llmi_session_seq_reserve(llmi_session* s, int n_seq) {
   return guard([&] {
     if (!s) throw status_error(LLMI_E_ARG, "seq_reserve: null pointer");
@@ -756,14 +767,18 @@ int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int
   });
 }
 
-int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
-                    const int32_t* targets, float* logprob, float* lse, int32_t* argmax) {
+// llmi_score_rows (top_n = 0) and llmi_score_rows_top
+static int score_rows_impl(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                           const int32_t* targets, float* logprob, float* lse, int32_t* argmax, int top_n,
+                           int32_t* top_ids, float* top_logprobs) {
   return guard([&] {
     if (!x16 || !w16) throw status_error(LLMI_E_ARG, "score_rows: null pointer");
     if (T <= 0 || V <= 0) throw status_error(LLMI_E_ARG, "score_rows: T and V must be positive");
     if (E <= 0 || E % 16 != 0) throw status_error(LLMI_E_SIZE, "score_rows: E must be a positive multiple of 16");
     const ScorePlan p = score_plan(T, V, E);
     if (!p.ok) throw status_error(LLMI_E_SIZE, "score_rows: shape too large");
+    if (top_n > 0 && !score_top_plan(p, top_n).ok)
+      throw status_error(LLMI_E_SIZE, "score_rows: the row and the tile keys do not fit the top-N pass's LDS (top_n)");
     if (targets)
       for (int i = 0; i < T; i++)
         if (targets[i] < -1 || targets[i] >= V) throw status_error(LLMI_E_RANGE, "score_rows: target id out of range (targets)");
@@ -773,8 +788,9 @@ int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int 
     uint16_t* wd = (uint16_t*)c.get(1, p.w_bytes);
     a.ms = (float2*)c.get(2, p.ms_bytes);
     a.key = (unsigned long long*)c.get(3, p.key_bytes);
-    // slot 4: targets, target logits, the three outputs
-    uint8_t* misc = (uint8_t*)c.get(4, (size_t)T * 20);
+    // slot 4: the f64 log-sum-exps, targets, target logits, the three outputs, the top-N ids and log-probs
+    uint8_t* misc0 = (uint8_t*)c.get(4, (size_t)T * (28 + 8 * (size_t)top_n));
+    uint8_t* misc = misc0 + (size_t)T * 8;
     int32_t* tg = (int32_t*)misc;
     a.tl = (float*)(misc + (size_t)T * 4);
     a.logprob = (float*)(misc + (size_t)T * 8);
@@ -791,12 +807,39 @@ int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int 
     a.E = E;
     a.softcap = softcap;
     a.targets = targets ? tg : nullptr;
+    if (top_n > 0) {
+      a.lse64 = (double*)misc0;
+      a.top_n = top_n;
+      a.top_id = (int32_t*)(misc + (size_t)T * 20);
+      a.top_lp = (float*)(misc + (size_t)T * 20 + (size_t)T * top_n * 4);
+    }
     launch_score_rows(a, c.stream);
+    if (top_n > 0) {
+      LLMI_HIP(hipMemcpyAsync(top_ids, a.top_id, (size_t)T * top_n * 4, hipMemcpyDeviceToHost, c.stream));
+      LLMI_HIP(hipMemcpyAsync(top_logprobs, a.top_lp, (size_t)T * top_n * 4, hipMemcpyDeviceToHost, c.stream));
+    }
     if (logprob) LLMI_HIP(hipMemcpyAsync(logprob, a.logprob, (size_t)T * 4, hipMemcpyDeviceToHost, c.stream));
     if (lse) LLMI_HIP(hipMemcpyAsync(lse, a.lse, (size_t)T * 4, hipMemcpyDeviceToHost, c.stream));
     if (argmax) LLMI_HIP(hipMemcpyAsync(argmax, a.argmax, (size_t)T * 4, hipMemcpyDeviceToHost, c.stream));
     LLMI_HIP(hipStreamSynchronize(c.stream));
   });
+}
+
+int llmi_score_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                    const int32_t* targets, float* logprob, float* lse, int32_t* argmax) {
+  return score_rows_impl(x16, w16, T, V, E, softcap, targets, logprob, lse, argmax, 0, nullptr, nullptr);
+}
+
+int llmi_score_rows_top(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
+                        const int32_t* targets, float* logprob, float* lse, int32_t* argmax, int top_n,
+                        int32_t* top_ids, float* top_logprobs) {
+  if (top_n < 1 || top_n > LLMI_SCORE_TOP_MAX || (V > 0 && top_n > V))
+    return guard([&] {
+      throw status_error(LLMI_E_RANGE, "score_rows_top: top_n outside 1 .. min(LLMI_SCORE_TOP_MAX, V) (top_n)");
+    });
+  if (!top_ids || !top_logprobs)
+    return guard([&] { throw status_error(LLMI_E_ARG, "score_rows_top: null pointer (top_ids / top_logprobs)"); });
+  return score_rows_impl(x16, w16, T, V, E, softcap, targets, logprob, lse, argmax, top_n, top_ids, top_logprobs);
 }
 
 int llmi_session_dump(llmi_session* s, const int32_t* tokens, int n_tokens, int pos, const char* path) {

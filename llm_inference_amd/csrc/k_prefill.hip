@@ -828,7 +828,10 @@ __global__ __launch_bounds__(512, 2) void prefill_gemm6_kernel(PrefillGemm16 a) 
   auto wait_ahead = [&](int ahead) {
     static_for<NS - 1>([&](auto kc) {
       constexpr int k = decltype(kc)::value, n = NS - 2 - k;
-      if (ahead == n) vm_wait<C::PW * n>();
+      if (ahead == n) {  // what this wave itself issued per stage (v5's rule): a wave with PW - 1 pieces that
+        if (full_last) vm_wait<C::PW * n>();  // waited for PW * n left n pieces of the current stage in flight
+        else vm_wait<(C::PW - 1) * n>();
+      }
     });
   };
   for (int c = 0; c < NS - 1 && c < nst; c++) issue(c);

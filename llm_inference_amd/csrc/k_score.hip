@@ -14,7 +14,9 @@
 //    lane, then the other half-wave), the 4 waves merged in wave order through LDS: one partial per (token,
 //    vocabulary tile).  The target's logit is written by the one lane that holds it.
 //  * score_merge_kernel: per token, max and key over the tiles, then sum_i s_i exp(m_i - M) in f64 (strided per
-//    thread in tile order, a fixed LDS tree across threads): deterministic, no float atomics.
+//    thread in tile order, a fixed LDS tree across threads): deterministic, no float atomics.  With ScoreArgs::lse64
+//    set it also leaves the f64 log-sum-exp, and the stored tile keys are what the top-N pass (k_score_top.hip) picks
+//    its tiles from.
 #include "kernels.h"
 #include "score_plan.h"
 
@@ -191,6 +193,7 @@ __global__ __launch_bounds__(256) void score_merge_kernel(ScoreArgs a, int n_vt)
     const double lse = M + log(sum);
     const int tgt = a.targets ? a.targets[tok] : -1;
     if (a.lse) a.lse[tok] = (float)lse;
+    if (a.lse64) a.lse64[tok] = lse;  // the top-N pass subtracts from the unrounded value, as the line below does
     if (a.logprob) a.logprob[tok] = tgt >= 0 ? (float)((double)a.tl[tok] - lse) : 0.0f;
     if (a.argmax) a.argmax[tok] = s_key[0] ? (int32_t)argmax_key_index(s_key[0]) : 0;  // (every logit NaN: id 0)
   }
@@ -198,7 +201,8 @@ __global__ __launch_bounds__(256) void score_merge_kernel(ScoreArgs a, int n_vt)
 
 // Row path: one f32 logits row (forward's, after the soft-cap)
 __global__ __launch_bounds__(1024) void score_reduce_row_kernel(const float* __restrict__ x, int n, int target,
-                                                                float* logprob, float* lse, int32_t* argmax) {
+                                                                float* logprob, float* lse, int32_t* argmax,
+                                                                double* lse64) {
   __shared__ double sh[1024];
   __shared__ float s_mx[1024];
   __shared__ unsigned long long s_key[1024];
@@ -233,6 +237,7 @@ __global__ __launch_bounds__(1024) void score_reduce_row_kernel(const float* __r
   if (t == 0) {
     const double l = M + log(sh[0]);
     if (lse) *lse = (float)l;
+    if (lse64) *lse64 = l;
     if (logprob) *logprob = target >= 0 ? (float)((double)x[target] - l) : 0.0f;
     if (argmax) *argmax = s_key[0] ? (int32_t)argmax_key_index(s_key[0]) : 0;
   }
@@ -244,16 +249,19 @@ void launch_score_rows(const ScoreArgs& a, hipStream_t s) {
   const ScorePlan p = score_plan(a.T, a.V, a.E);
   if (!p.ok || a.xstride < a.E || a.xstride % 8 != 0) throw std::runtime_error("score_rows: T, V >= 1 and E % 16 == 0");
   if (!a.x16 || !a.w16 || !a.ms || !a.key || !a.tl) throw std::runtime_error("score_rows: null buffer");
+  if (a.top_n > 0 && !a.lse64) throw std::runtime_error("score_rows: top_n needs lse64");
   hipLaunchKernelGGL(score_partials_kernel, dim3(p.n_vtiles), dim3(256), 0, s, a, p.n_vtiles);
   LLMI_HIP(hipGetLastError());
   hipLaunchKernelGGL(score_merge_kernel, dim3(a.T), dim3(256), 0, s, a, p.n_vtiles);
   LLMI_HIP(hipGetLastError());
+  if (a.top_n > 0) launch_score_top(a, s);
 }
 
 void launch_score_reduce_row(const float* logits, int V, int target, float* logprob, float* lse, int32_t* argmax,
-                             hipStream_t s) {
+                             hipStream_t s, double* lse64) {
   if (V < 1 || target >= V) throw std::runtime_error("score_reduce_row: target outside the row");
-  hipLaunchKernelGGL(score_reduce_row_kernel, dim3(1), dim3(1024), 0, s, logits, V, target, logprob, lse, argmax);
+  hipLaunchKernelGGL(score_reduce_row_kernel, dim3(1), dim3(1024), 0, s, logits, V, target, logprob, lse, argmax,
+                     lse64);
   LLMI_HIP(hipGetLastError());
 }
 

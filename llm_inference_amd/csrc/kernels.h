@@ -116,12 +116,24 @@ struct ScoreArgs {
   float* logprob = nullptr;
   float* lse = nullptr;
   int32_t* argmax = nullptr;
+  // the top-N pass (k_score_top.hip; section 11.6), top_n = 0: none.  lse64 [T] (the merge's f64 log-sum-exp before
+  // its rounding, stored whenever the pointer is set), top_id / top_lp [T][top_n]: the top_n largest logits of each
+  // token, descending (ties: the lower id), top_lp = (float)((double)logit - lse64).
+  double* lse64 = nullptr;
+  int top_n = 0;
+  int32_t* top_id = nullptr;
+  float* top_lp = nullptr;
 };
 void launch_score_rows(const ScoreArgs& a, hipStream_t s);
+// the third launch of launch_score_rows when a.top_n > 0 (after the merge: reads a.key and a.lse64)
+void launch_score_top(const ScoreArgs& a, hipStream_t s);
 // Row path: the same three results from one f32 logits row (f64 accumulation, the same tie rule) into
-// logprob[0] / lse[0] / argmax[0]; target -1: none.
+// logprob[0] / lse[0] / argmax[0]; target -1: none.  lse64 (may be null): the f64 log-sum-exp before its rounding.
 void launch_score_reduce_row(const float* logits, int V, int target, float* logprob, float* lse, int32_t* argmax,
-                             hipStream_t s);
+                             hipStream_t s, double* lse64 = nullptr);
+// Row path's top-N: top_id / top_lp [top_n] of one f32 logits row, the fused pass's rule; lse64: the reduce's.
+void launch_score_top_row(const float* logits, int V, int top_n, const double* lse64, int32_t* top_id, float* top_lp,
+                          hipStream_t s);
 
 // ---- lookup decoding (k_lookup.hip) ----
 struct SeqRow;     // (session_kernels.h)

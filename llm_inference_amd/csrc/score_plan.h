@@ -51,6 +51,43 @@ inline ScorePlan score_plan(long long T, long long V, long long E) {
   return p;
 }
 
+// ---- the top-N pass (k_score_top.hip) ----
+constexpr int SCORE_TOP_MAX = 32;                  // include/llmi.h LLMI_SCORE_TOP_MAX
+constexpr size_t SCORE_TOP_LDS_MAX = 63 * 1024;    // dynamic LDS of a work-group (its static arrays take < 1 KB)
+
+struct ScoreTopPlan {
+  int top_n = 0;
+  int n_pick = 0;        // vocabulary tiles rescored per token: min(top_n, n_vtiles)
+  int n_ksteps = 0;      // MFMA k steps of a logit's chain: 4 per stage, the last stage's zero-padded ones included
+  size_t key_off = 0;    // LDS: the token's f16 row [E] at 0, then at key_off the keys --
+  size_t key_slots = 0;  //   first the token's n_vtiles tile keys, then its n_pick * SCORE_VT candidates
+  size_t lds_bytes = 0;
+  size_t lse64_bytes = 0;  // f64 log-sum-exp [T], left by the merge
+  size_t id_bytes = 0;     // int32 ids [T][top_n]
+  size_t lp_bytes = 0;     // f32 log-probs [T][top_n]
+  bool ok = false;
+};
+
+// 1 <= top_n <= min(SCORE_TOP_MAX, V), and the row plus the keys must fit the work-group's LDS (V up to about
+// 800,000 rows at E = 5376).
+inline ScoreTopPlan score_top_plan(const ScorePlan& p, long long top_n) {
+  ScoreTopPlan q;
+  if (!p.ok || top_n < 1 || top_n > SCORE_TOP_MAX || top_n > p.V) return q;
+  q.top_n = (int)top_n;
+  q.n_pick = q.top_n < p.n_vtiles ? q.top_n : p.n_vtiles;
+  q.n_ksteps = p.n_stages * (SCORE_KS / 16);
+  q.key_off = ((size_t)p.E * 2 + 15) / 16 * 16;
+  const size_t cand = (size_t)q.n_pick * SCORE_VT;
+  q.key_slots = cand > (size_t)p.n_vtiles ? cand : (size_t)p.n_vtiles;
+  q.lds_bytes = q.key_off + q.key_slots * 8;
+  if (q.lds_bytes > SCORE_TOP_LDS_MAX) return q;
+  q.lse64_bytes = (size_t)p.T * 8;
+  q.id_bytes = (size_t)p.T * (size_t)q.top_n * 4;
+  q.lp_bytes = (size_t)p.T * (size_t)q.top_n * 4;
+  q.ok = true;
+  return q;
+}
+
 // The global row a tile's local row reads: rows past the edge re-read the last valid row (their results are masked),
 // so no load ever leaves the table or the rows.
 inline long long score_clamped_row(long long tile, int tile_rows, int local, long long n_rows) {

@@ -1955,6 +1955,9 @@ void Session::ensure_score_buffers(int cap) {
   sc_lp_ = dalloc<float>((size_t)cap);
   sc_lse_ = dalloc<float>((size_t)cap);
   sc_amax_ = dalloc<int32_t>((size_t)cap);
+  sc_lse64_ = dalloc<double>((size_t)cap);
+  sc_top_id_ = dalloc<int32_t>((size_t)cap * SCORE_TOP_MAX);
+  sc_top_lp_ = dalloc<float>((size_t)cap * SCORE_TOP_MAX);
   sc_cap_ = cap;
 }
 
@@ -1973,6 +1976,10 @@ ScoreArgs Session::score_args(const uint16_t* x16, int T, const int32_t* targets
   a.logprob = sc_lp_;
   a.lse = sc_lse_;
   a.argmax = sc_amax_;
+  a.lse64 = sc_top_n_ > 0 ? sc_lse64_ : nullptr;  // (top_n = 0: the launches as they were)
+  a.top_n = sc_top_n_;
+  a.top_id = sc_top_id_;
+  a.top_lp = sc_top_lp_;
   return a;
 }
 
@@ -1997,6 +2004,11 @@ void Session::score_chunk(int c0, int T, hipStream_t s) {
   LLMI_HIP(hipMemcpyAsync(sc_h_lp_.data() + c0, sc_lp_, (size_t)T * 4, hipMemcpyDeviceToHost, s));
   LLMI_HIP(hipMemcpyAsync(sc_h_lse_.data() + c0, sc_lse_, (size_t)T * 4, hipMemcpyDeviceToHost, s));
   LLMI_HIP(hipMemcpyAsync(sc_h_amax_.data() + c0, sc_amax_, (size_t)T * 4, hipMemcpyDeviceToHost, s));
+  if (sc_top_n_ > 0) {  // [T][top_n], contiguous: the chunk's slice of the call's [n][top_n]
+    const size_t o = (size_t)c0 * sc_top_n_, b = (size_t)T * sc_top_n_ * 4;
+    LLMI_HIP(hipMemcpyAsync(sc_h_top_id_.data() + o, sc_top_id_, b, hipMemcpyDeviceToHost, s));
+    LLMI_HIP(hipMemcpyAsync(sc_h_top_lp_.data() + o, sc_top_lp_, b, hipMemcpyDeviceToHost, s));
+  }
   // (the host vectors are pageable: each copy has left the chunk's buffers when it returns)
 }
 
@@ -2029,11 +2041,23 @@ void Session::score_run(const int32_t* tokens, int n, int pos) {
     sc_lse_ = dalloc<float>(std::max(sc_cap_, 1));
     sc_amax_ = dalloc<int32_t>(std::max(sc_cap_, 1));
   }
+  if (!sc_lse64_) {
+    sc_lse64_ = dalloc<double>(std::max(sc_cap_, 1));
+    sc_top_id_ = dalloc<int32_t>((size_t)std::max(sc_cap_, 1) * SCORE_TOP_MAX);
+    sc_top_lp_ = dalloc<float>((size_t)std::max(sc_cap_, 1) * SCORE_TOP_MAX);
+  }
   for (int i = 0; i < n; i++) {
     set_token_pos(tokens[i], pos + i, i == 0);
     if (trace_fn_) record_step(stream_, false);
     else run_step(STEP_LOGITS);
-    launch_score_reduce_row(logits_, vocab_, sc_h_tgt_[(size_t)i], sc_lp_, sc_lse_, sc_amax_, stream_);
+    launch_score_reduce_row(logits_, vocab_, sc_h_tgt_[(size_t)i], sc_lp_, sc_lse_, sc_amax_, stream_,
+                            sc_top_n_ > 0 ? sc_lse64_ : nullptr);  // (top_n = 0: the launch as it was)
+    if (sc_top_n_ > 0) {
+      const size_t o = (size_t)i * sc_top_n_, b = (size_t)sc_top_n_ * 4;
+      launch_score_top_row(logits_, vocab_, sc_top_n_, sc_lse64_, sc_top_id_, sc_top_lp_, stream_);
+      LLMI_HIP(hipMemcpyAsync(sc_h_top_id_.data() + o, sc_top_id_, b, hipMemcpyDeviceToHost, stream_));
+      LLMI_HIP(hipMemcpyAsync(sc_h_top_lp_.data() + o, sc_top_lp_, b, hipMemcpyDeviceToHost, stream_));
+    }
     tap("sc_lse", -1, sc_lse_, 4, stream_);
     tap("sc_logprob", -1, sc_lp_, 4, stream_);
     tap("sc_argmax", -1, sc_amax_, 4, stream_);
@@ -2044,8 +2068,12 @@ void Session::score_run(const int32_t* tokens, int n, int pos) {
 }
 
 void Session::score(const int32_t* tokens, int n, int pos, const int32_t* targets, float* logprob, float* lse,
-                    int32_t* argmax) {
+                    int32_t* argmax, int top_n, int32_t* top_ids, float* top_logprobs) {
   if (tp_) throw status_error(LLMI_E_ARG, "score: one device only (tensor-parallel session)");
+  if (top_n < 0 || top_n > std::min(SCORE_TOP_MAX, vocab_))
+    throw status_error(LLMI_E_RANGE, "score: top_n outside 1 .. min(LLMI_SCORE_TOP_MAX, vocabulary) (top_n)");
+  if (top_n > 0 && score_path() == 1 && !score_top_plan(score_plan(1, vocab_, hp_.n_embd), top_n).ok)
+    throw status_error(LLMI_E_SIZE, "score: the vocabulary's tile keys do not fit the top-N pass's LDS (top_n)");
   if (n <= 0) throw status_error(LLMI_E_ARG, "score: no tokens (n_tokens)");
   if (pos < 0 || pos + n > max_ctx_) throw status_error(LLMI_E_RANGE, "score: context overflow (pos + n_tokens)");
   for (int i = 0; i < n; i++)
@@ -2057,9 +2085,17 @@ void Session::score(const int32_t* tokens, int n, int pos, const int32_t* target
     sc_h_tgt_[(size_t)i] = t;
   }
   ensure_usable();
+  sc_top_n_ = top_n;
+  ScopeExit top_off{[&] { sc_top_n_ = 0; }};
+  sc_h_top_id_.assign((size_t)n * top_n, 0);
+  sc_h_top_lp_.assign((size_t)n * top_n, 0.0f);
   score_run(tokens, n, pos);
   LLMI_HIP(hipStreamSynchronize(stream_));
   check_device_error();
+  if (top_n > 0) {
+    std::memcpy(top_ids, sc_h_top_id_.data(), (size_t)n * top_n * 4);
+    std::memcpy(top_logprobs, sc_h_top_lp_.data(), (size_t)n * top_n * 4);
+  }
   if (logprob) std::memcpy(logprob, sc_h_lp_.data(), (size_t)n * 4);
   if (lse) std::memcpy(lse, sc_h_lse_.data(), (size_t)n * 4);
   if (argmax) std::memcpy(argmax, sc_h_amax_.data(), (size_t)n * 4);

@@ -99,9 +99,9 @@ class Session {
   void forward_dump(const int32_t* tokens, int n_tokens, int pos, const char* path);
   void forward_trace(const int32_t* tokens, int n_tokens, int pos, bool gen, llmi_trace_fn fn, void* user,
                      bool score = false);
-  // llmi_session_score
+  // llmi_session_score / llmi_session_score_top (top_n = 0: no top-N pass)
   void score(const int32_t* tokens, int n_tokens, int pos, const int32_t* targets, float* logprob, float* lse,
-             int32_t* argmax);
+             int32_t* argmax, int top_n = 0, int32_t* top_ids = nullptr, float* top_logprobs = nullptr);
   // several sequences per step (session_batch.cpp)
   void seq_reserve(int n_seq);
   int n_seq() const { return n_seq_; }
@@ -353,6 +353,13 @@ class Session {
   float *sc_tl_ = nullptr, *sc_lp_ = nullptr, *sc_lse_ = nullptr;
   std::vector<int32_t> sc_h_tgt_, sc_h_amax_;  // host: the call's resolved targets, its results
   std::vector<float> sc_h_lp_, sc_h_lse_;
+  // the top-N pass (section 11.6): sc_top_n_ > 0 only inside a score() call that asked for it
+  int sc_top_n_ = 0;
+  double* sc_lse64_ = nullptr;   // [cap]
+  int32_t* sc_top_id_ = nullptr;  // [cap][SCORE_TOP_MAX] allocated, [T][sc_top_n_] in use
+  float* sc_top_lp_ = nullptr;
+  std::vector<int32_t> sc_h_top_id_;
+  std::vector<float> sc_h_top_lp_;
   // several sequences per step: KV slots (slot 0 = L_[l].kc / vc) and the batch step's device-resident rows
   int n_seq_ = 1;
   bool seq_reserved_ = false;

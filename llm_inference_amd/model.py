@@ -270,6 +270,23 @@ class Model:
         self.last_argmax = int(am[-1])
         return ScoreResult(lp, lse, am, resolve_targets(t, tg))
 
+    def score_top(self, tokens: Sequence[int], top_n: int, pos: int = 0,
+                  targets: Optional[Sequence[int]] = None) -> ScoreResult:
+        """llmi_session_score_top: score() and, per position, the top_n most likely ids with their log-probs
+        (.top_ids int32 [n][top_n], most likely first, ties by lower id; .top_logprobs float32 [n][top_n]; DESIGN.md
+        section 11.6).  .logprobs / .lse / .argmax are score()'s bits.  1 <= top_n <= min(32, vocabulary)."""
+        t = np.ascontiguousarray(tokens, np.int32)
+        tg = None if targets is None else np.ascontiguousarray(targets, np.int32)
+        if tg is not None and tg.shape != t.shape:
+            raise ValueError("targets must have one id per token (-1: no target)")
+        n, k = t.size, max(int(top_n), 0)
+        lp, lse, am = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        ids, tlp = np.zeros((n, k), np.int32), np.zeros((n, k), np.float32)
+        check(lib().llmi_session_score_top(self.h, ptr(t), n, pos, ptr(tg) if tg is not None else None,
+                                           ptr(lp), ptr(lse), ptr(am), int(top_n), ptr(ids), ptr(tlp)))
+        self.last_argmax = int(am[-1])
+        return ScoreResult(lp, lse, am, resolve_targets(t, tg), ids, tlp)
+
     def perplexity(self, tokens: Sequence[int]) -> float:
         """exp(nll / count) of the tokens after the first, each scored given the ones before it."""
         return self.score(tokens).perplexity

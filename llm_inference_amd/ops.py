@@ -218,6 +218,27 @@ def score_rows(x16, w16, targets=None, softcap: float = 0.0):
     return ScoreResult(lp, lse, am, tg if tg is not None else np.full(T, -1, np.int32))
 
 
+def score_rows_top(x16, w16, top_n: int, targets=None, softcap: float = 0.0):
+    """llmi_score_rows_top: score_rows and, per row, the top_n largest logits' ids (.top_ids int32 [T][top_n],
+    descending by value, ties by lower id) with their log-probs (.top_logprobs float32 [T][top_n]; DESIGN.md section
+    11.6).  1 <= top_n <= min(32, V), else LLMI_E_RANGE."""
+    from .score import ScoreResult
+    x, w = _f16_bits(x16), _f16_bits(w16)
+    if x.ndim != 2 or w.ndim != 2 or x.shape[1] != w.shape[1]:
+        raise ValueError("score_rows_top: x16 [T][E] and w16 [V][E]")
+    T, E = x.shape
+    tg = None if targets is None else np.ascontiguousarray(targets, np.int32)
+    if tg is not None and tg.shape != (T,):
+        raise ValueError("score_rows_top: one target per row (-1: none)")
+    k = max(int(top_n), 0)
+    lp, lse, am = np.zeros(T, np.float32), np.zeros(T, np.float32), np.zeros(T, np.int32)
+    ids, tlp = np.zeros((T, k), np.int32), np.zeros((T, k), np.float32)
+    check(lib().llmi_score_rows_top(ptr(x), ptr(w), T, w.shape[0], E, float(softcap),
+                                    ptr(tg) if tg is not None else None, ptr(lp), ptr(lse), ptr(am), int(top_n),
+                                    ptr(ids), ptr(tlp)))
+    return ScoreResult(lp, lse, am, tg if tg is not None else np.full(T, -1, np.int32), ids, tlp)
+
+
 def logits_rows_rb(E: int) -> int:
     """llmi_logits_rows_rb: the activation rows that share one read of the table in logits_rows at width E (0: the
     width is not supported).  No GPU work."""

@@ -9,13 +9,17 @@ import numpy as np
 class ScoreResult:
     """Per position i: logprobs[i] = log p(targets[i] | tokens[:i + 1]) (0.0 where the position has no target),
     lse[i] = log sum_v exp(logit_i[v]), argmax[i] = the greedy id (first maximal index).  targets holds the ids
-    that were scored, -1 = none."""
+    that were scored, -1 = none.  From Model.score_top / ops.score_rows_top also top_ids (int32 [T][N]) and
+    top_logprobs (float32 [T][N]): the N most likely ids of position i, most likely first (ties: the lower id), and
+    their log-probs; both None otherwise."""
 
-    def __init__(self, logprobs, lse, argmax, targets):
+    def __init__(self, logprobs, lse, argmax, targets, top_ids=None, top_logprobs=None):
         self.logprobs = np.asarray(logprobs, np.float32)
         self.lse = np.asarray(lse, np.float32)
         self.argmax = np.asarray(argmax, np.int32)
         self.targets = np.asarray(targets, np.int32)
+        self.top_ids = None if top_ids is None else np.asarray(top_ids, np.int32)
+        self.top_logprobs = None if top_logprobs is None else np.asarray(top_logprobs, np.float32)
 
     @property
     def count(self) -> int:

@@ -92,6 +92,25 @@ int main() {
   // shapes the planner must turn away
   CHECK(!score_plan(0, 10, 16).ok && !score_plan(3, 0, 16).ok && !score_plan(3, 10, 24).ok && !score_plan(3, 10, 0).ok);
   CHECK(!score_plan(3, 10, 1LL << 31).ok && !score_plan(1LL << 31, 10, 16).ok);
+  // the top-N pass: the LDS holds the row, then whichever is larger of the tile keys and the candidates
+  for (const auto& s : shapes)
+    for (int n : {1, 5, 32}) {
+      const ScorePlan p = score_plan(s[0], s[1], s[2]);
+      const ScoreTopPlan q = score_top_plan(p, n);
+      if (n > s[1]) {
+        CHECK(!q.ok);
+        continue;
+      }
+      CHECK(q.ok && q.n_pick >= 1 && q.n_pick <= n && q.n_pick <= p.n_vtiles && q.n_ksteps * 16 >= p.E);
+      CHECK(q.key_off % 16 == 0 && q.key_off >= (size_t)p.E * 2);
+      CHECK(q.key_slots >= (size_t)p.n_vtiles && q.key_slots >= (size_t)q.n_pick * SCORE_VT);
+      CHECK(q.lds_bytes == q.key_off + q.key_slots * 8 && q.lds_bytes <= SCORE_TOP_LDS_MAX);
+      CHECK(q.id_bytes == (size_t)s[0] * n * 4 && q.lp_bytes == q.id_bytes && q.lse64_bytes == (size_t)s[0] * 8);
+    }
+  const ScoreTopPlan real = score_top_plan(score_plan(512, 262208, 5376), 32);
+  CHECK(real.ok && real.n_pick == 32 && real.lds_bytes == 10752 + 32 * 128 * 8);
+  CHECK(!score_top_plan(score_plan(4, 100, 16), 0).ok && !score_top_plan(score_plan(4, 100, 16), 33).ok);
+  CHECK(!score_top_plan(score_plan(4, 1 << 20, 5376), 1).ok);  // 8192 tile keys beside the row: past the LDS
   std::puts("score_plan_check OK");
   return 0;
 }

@@ -1,6 +1,6 @@
 """Score a random prompt on the device (Model.score) and time it.
 
-    python scripts/score_prompt.py --config gemma-3-4b --n 512 [--reps 7] [--prefix-n 32]
+    python scripts/score_prompt.py --config gemma-3-4b --n 512 [--reps 7] [--prefix-n 32] [--top N]
 
 Prints the prompt's nll and perplexity, then, warm (two untimed calls first), the median and the min .. max of
 --reps synchronous calls of
@@ -9,6 +9,8 @@ Prints the prompt's nll and perplexity, then, warm (two untimed calls first), th
   (c) time_kernel(9)           the fused scorer's two launches over the last chunk, with its FLOP and byte rates,
   (d) score(prompt) with LLMI_NO_PREFILL=1: the row path (token loop, full logits, f64 row reduce), same session,
 and, with --prefix-n K, the only route without score(): one forward per prefix over the first K tokens.
+With --top N (fused path): (t) score_top(prompt, N) alternating with score(prompt), the added pass's time, its table
+stream n N 128 E 2 bytes and the rate that makes, and one forward with full logits (x n: the route without it).
 """
 import argparse
 import os
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--config", default="gemma-3-4b", choices=sorted(CONFIGS))
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--top", type=int, default=0, help="also time score_top(prompt, N) against score(prompt)")
     ap.add_argument("--prefix-n", type=int, default=0, help="also time one forward per prefix over the first K tokens")
     a = ap.parse_args()
     os.environ.pop("LLMI_NO_PREFILL", None)
@@ -70,6 +73,29 @@ def main():
               f"{t_byte:.1f} us of HBM) = {max(t_flop, t_byte) / us:.3f} of the kernel time", flush=True)
     else:
         print("(c) time_kernel(9)  0 / 0: the row path is in use", flush=True)
+    if a.top > 0 and info.score_path == 1:
+        rt = m.score_top(prompt, a.top)
+        assert (rt.top_ids[:, 0] == r.argmax).all()
+        m.forward(prompt, 0)
+        t0 = time.perf_counter()
+        m.forward(prompt, 0)
+        t_fwd = (time.perf_counter() - t0) * 1e3
+        plain_ms, top_ms = [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            m.score(prompt)
+            plain_ms.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            m.score_top(prompt, a.top)
+            top_ms.append((time.perf_counter() - t0) * 1e3)
+        tp0 = (statistics.median(plain_ms), min(plain_ms), max(plain_ms))
+        tp1 = (statistics.median(top_ms), min(top_ms), max(top_ms))
+        stream, added = a.n * a.top * 128 * cfg.n_embd * 2.0, tp1[0] - tp0[0]
+        tiles = len({(i, int(v) // 128) for i, row in enumerate(rt.top_ids) for v in row})
+        print(f"(t) score_top(prompt, {a.top}) {fmt(tp1)}, alternating with score(prompt) at {fmt(tp0)}: the pass adds "
+              f"{added:.3f} ms for a table stream of {stream / 1e9:.3f} GB = {stream / max(added, 1e-9) / 1e9:.1f} TB/s; "
+              f"the ids fall in {tiles / a.n:.2f} tiles per token; one forward with full logits {t_fwd:.3f} ms, "
+              f"x {a.n} = {t_fwd * a.n / 1e3:.2f} s (extrapolated, not run)", flush=True)
     # the row path on the same session (LLMI_NO_PREFILL is read at the call), the two alternating
     os.environ["LLMI_NO_PREFILL"] = "1"
     assert m.get_info().score_path == 2
