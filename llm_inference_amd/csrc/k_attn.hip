@@ -825,8 +825,10 @@ constexpr size_t block_attn_lds() {  // s_k + s_v (32-key tiles) + s_red
 constexpr int WT_W8 = 3;  // Q8_0 weights in the block (layer_body W8), beside the kq formats WT_Q4_K / WT_Q6_K
 
 // PXF: the qkv prologue / o epilogue honour the fused exchange (tensor-parallel ranks; layer_body PXF)
+// QORD: the qkv role's prologue order (layer_body ORD; PRO, Q4_0).  Only the qkv work-groups take its barrier:
+// roles are uniform per work-group
 template <int HD, int G, int QR, int QP, int QE, int QROLE, int OR, int OP, int OE, int WTQ = 0, int WTQB = 0,
-          int WTO = 0, int KVD = 1, int NS = ATTN_NSPLIT, bool PXF = false>
+          int WTO = 0, int KVD = 1, int NS = ATTN_NSPLIT, bool PXF = false, int QORD = 0>
 __global__ __launch_bounds__(256) void attn_block_kernel(LayerGemv qg, LayerGemv og, AttnArgs aa, QKVArgs qa,
                                                         BlockSync bs, int nq, LayerGemv qgb, int nqa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
@@ -843,8 +845,8 @@ __global__ __launch_bounds__(256) void attn_block_kernel(LayerGemv qg, LayerGemv
       }
     }
     if (!second)
-      layer_body<QR, 4, QP, QE, QROLE, false, true, SYNC_SIG, 0, WTQ == WT_W8, WTQ == WT_W8 ? 0 : WTQ, 0, PXF>(qg, b, s_dyn,
-                                                                                                           bs);
+      layer_body<QR, 4, QP, QE, QROLE, false, true, SYNC_SIG, 0, WTQ == WT_W8, WTQ == WT_W8 ? 0 : WTQ, 0, PXF, false,
+                 QORD>(qg, b, s_dyn, bs);
   } else if (b - nq < na) {
     b -= nq;
     constexpr int KS = attn_ks<HD, G>();
@@ -864,7 +866,7 @@ using BlockFn = void (*)(dim3, size_t, const LayerGemv&, const LayerGemv&, const
                          const BlockSync&, int, const LayerGemv&, int, hipStream_t);
 
 template <int HD, int G, int QR, int QP, int QE, int QROLE, int OR, int OP, int OE, int WTQ, int WTQB, int WTO,
-          int KVD = 1, int NS = ATTN_NSPLIT>
+          int KVD = 1, int NS = ATTN_NSPLIT, int QORD = 0>
 void block_launch(dim3 grid, size_t lds, const LayerGemv& qg, const LayerGemv& og, const AttnArgs& aa,
                   const QKVArgs& qa, const BlockSync& bs, int nq, const LayerGemv& qgb, int nqa, hipStream_t s) {
   if (qg.px || og.px) {  // the fused-exchange variant (tensor-parallel ranks): co-resident too, or refused
@@ -880,12 +882,12 @@ void block_launch(dim3 grid, size_t lds, const LayerGemv& qg, const LayerGemv& o
   }
   KernelTiming& kt = kernel_timing();
   if (kt.start) {  // bench: events signalled by this dispatch itself (its duration as rocprofv3 reports it)
-    hipExtLaunchKernelGGL((attn_block_kernel<HD, G, QR, QP, QE, QROLE, OR, OP, OE, WTQ, WTQB, WTO, KVD, NS>), grid, dim3(256),
+    hipExtLaunchKernelGGL((attn_block_kernel<HD, G, QR, QP, QE, QROLE, OR, OP, OE, WTQ, WTQB, WTO, KVD, NS, false, QORD>), grid, dim3(256),
                           (uint32_t)lds, s, kt.start, kt.stop, 0u, qg, og, aa, qa, bs, nq, qgb, nqa);
     kt = KernelTiming{};
     return;
   }
-  hipLaunchKernelGGL((attn_block_kernel<HD, G, QR, QP, QE, QROLE, OR, OP, OE, WTQ, WTQB, WTO, KVD, NS>), grid, dim3(256), lds, s,
+  hipLaunchKernelGGL((attn_block_kernel<HD, G, QR, QP, QE, QROLE, OR, OP, OE, WTQ, WTQB, WTO, KVD, NS, false, QORD>), grid, dim3(256), lds, s,
                      qg, og, aa, qa, bs, nq, qgb, nqa);
 }
 
@@ -898,6 +900,19 @@ struct BlockCfg {
   int wtq, wtqb, wto;  // weight formats (layer_body WT): qkv, second qkv weight (0: none), o
   int kvd;             // virtual kv heads per cache head (attention work-groups of g / kvd q heads)
   int ns = ATTN_NSPLIT;  // key-range splits per kv head
+  // the qkv role's prologue order (layer_body ORD; LLMI_PRO_ORDER): the instances with the operand barrier and
+  // with the split issue beside the parent's (fn / kern), and the one launched by default
+  BlockFn fn_bar = nullptr, fn_split = nullptr;
+  const void *kern_bar = nullptr, *kern_split = nullptr;
+  int ord = PRO_ORDER_PARENT;
+  BlockFn pick_fn() const {
+    const int o = fn_bar ? pro_order(ord) : PRO_ORDER_PARENT;
+    return o == PRO_ORDER_SPLIT ? fn_split : o == PRO_ORDER_BARRIER ? fn_bar : fn;
+  }
+  const void* pick_kern() const {
+    const int o = fn_bar ? pro_order(ord) : PRO_ORDER_PARENT;
+    return o == PRO_ORDER_SPLIT ? kern_split : o == PRO_ORDER_BARRIER ? kern_bar : kern;
+  }
 };
 #define LLMI_BCFGW(NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, WTQ, WTQB, WTO)                          \
   {NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, block_attn_lds<HD, G>(),                                  \
@@ -915,6 +930,19 @@ struct BlockCfg {
   LLMI_BCFGVW(NBQ, NBO, HD, GM, KVD, QROLE, QR, QP, QE, OR, OP, OE, 0)
 #define LLMI_BCFG(NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE) \
   LLMI_BCFGW(NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, 0, 0, 0)
+// Q4_0 PRO entry with the qkv role's ORD instances (SPLIT: its ORD_SPLIT groups; ORD: the default order)
+#define LLMI_BCFGO_I(HD, G, QROLE, QR, QP, QE, OR, OP, OE, QORD) \
+  block_launch<HD, G, QR, QP, QE, QROLE, OR, OP, OE, 0, 0, 0, 1, ATTN_NSPLIT, QORD>
+#define LLMI_BCFGO_K(HD, G, QROLE, QR, QP, QE, OR, OP, OE, QORD) \
+  reinterpret_cast<const void*>(                                 \
+      &attn_block_kernel<HD, G, QR, QP, QE, QROLE, OR, OP, OE, 0, 0, 0, 1, ATTN_NSPLIT, false, QORD>)
+#define LLMI_BCFGO(NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, SPLIT, ORD)                                  \
+  {NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, block_attn_lds<HD, G>(),                                      \
+   LLMI_BCFGO_I(HD, G, QROLE, QR, QP, QE, OR, OP, OE, 0), LLMI_BCFGO_K(HD, G, QROLE, QR, QP, QE, OR, OP, OE, 0), \
+   0, 0, 0, 1, ATTN_NSPLIT,                                                                                      \
+   LLMI_BCFGO_I(HD, G, QROLE, QR, QP, QE, OR, OP, OE, ORD_BAR), LLMI_BCFGO_I(HD, G, QROLE, QR, QP, QE, OR, OP, OE, SPLIT), \
+   LLMI_BCFGO_K(HD, G, QROLE, QR, QP, QE, OR, OP, OE, ORD_BAR), LLMI_BCFGO_K(HD, G, QROLE, QR, QP, QE, OR, OP, OE, SPLIT), \
+   ORD}
 // NS key-range splits per kv head instead of ATTN_NSPLIT (Q4_0)
 #define LLMI_BCFGS(NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, NS)                                            \
   {NBQ, NBO, HD, G, QROLE, QR, QP, QE, OR, OP, OE, block_attn_lds<HD, G>(),                                        \
@@ -926,7 +954,7 @@ const BlockCfg kBlockCfgs[] = {
     // 4B: qkv 4096 rows -> 256 WGs, o 2560 -> 80 WGs (8 rows per wave: fewer
     // work-groups polling the merged blocks; A/B 913-915 vs 910 tok/s with 4
     // rows per wave (160 WGs), 902 with 2 (320 WGs))
-    LLMI_BCFG(80, 64, 256, 2, ROLE_PRO, 4, 5, 10, 8, 8, 1),
+    LLMI_BCFGO(80, 64, 256, 2, ROLE_PRO, 4, 5, 10, 8, 8, 1, LLMI_QKV_SPLIT, LLMI_QKV_ORDER),
     LLMI_BCFG(80, 64, 256, 2, ROLE_PLAIN, 4, 5, 1, 8, 8, 1),   // 4B layer 0
     // 1B: GQA group 4 as two virtual kv heads of 2 (64 attention WGs, two merges of 2 heads)
     LLMI_BCFGV(36, 32, 256, 4, 2, ROLE_PRO, 4, 3, 5, 4, 2, 1),
@@ -1012,7 +1040,7 @@ static bool block_co_resident(const BlockCfg& c, const BlockGeom& g) {
       return false;
   }
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c.kern, 256, g.lds) != hipSuccess) return false;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c.pick_kern(), 256, g.lds) != hipSuccess) return false;
   const long capacity = (long)std::max(0, per_cu - 1) * n_cu;
   return g.nq + g.na + g.no <= capacity;
 }
@@ -1075,7 +1103,7 @@ int launch_attn_block(const DevWeight& wqkv, const DevWeight* wqkv_b, LayerGemv 
   if (og.px && og.px_out >= 0 && bg.no > PX_MAX_CS) throw std::runtime_error("attention block: more fused-exchange producers than checksum slots");
   if (qg.px && qg.px_in >= 0 && (qg.px_in_nwg <= 0 || qg.px_in_nwg > PX_MAX_CS)) throw std::runtime_error("attention block: fused exchange read without its producer count");
   bs.done_n = (unsigned)(bg.no + av.n_head_kv);  // the o work-groups and the kv heads' final merges (k_attn: role 1)
-  c.fn(dim3(bg.nq + bg.na + bg.no), bg.lds, qg, og, av, qa, bs, bg.nq, qgb, nqa, s);
+  c.pick_fn()(dim3(bg.nq + bg.na + bg.no), bg.lds, qg, og, av, qa, bs, bg.nq, qgb, nqa, s);
   LLMI_HIP(hipGetLastError());
   return bg.no;
 }

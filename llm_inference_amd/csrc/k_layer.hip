@@ -33,10 +33,10 @@ namespace {
 
 // PXF: the fused-exchange variant (tensor-parallel ranks: a.px set; layer_body PXF)
 template <int R, int NW, int P, int E, int ROLE, bool MULTI, bool EARLY, int PE = 0, bool W8 = false, int WT = 0,
-          int RW = 0, bool PXF = false, bool TO = false>
+          int RW = 0, bool PXF = false, bool TO = false, int ORD = 0>
 __global__ __launch_bounds__(NW * 64 + (role_help(ROLE) ? E * 64 : 0)) void gemv_q4_0_layer(LayerGemv a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-  layer_body<R, NW, P, E, ROLE, MULTI, EARLY, 0, PE, W8, WT, RW, PXF, TO>(a, blockIdx.x, s_dyn, BlockSync{});
+  layer_body<R, NW, P, E, ROLE, MULTI, EARLY, 0, PE, W8, WT, RW, PXF, TO, ORD>(a, blockIdx.x, s_dyn, BlockSync{});
 }
 
 // K-quant q|k|v of two weight types in one launch (Q4_K_M: q, k Q4_K, v Q6_K):
@@ -66,9 +66,10 @@ using LaunchFn = void (*)(dim3, size_t, const LayerGemv&, hipStream_t);
 using Launch2Fn = void (*)(dim3, size_t, const LayerGemv&, const LayerGemv&, int, hipStream_t);
 
 // TO: the tail passes' offsets fixed before the head is issued (layer_body.h tail_offsets); the fused-exchange
-// variant keeps the late offsets
+// variant keeps the late offsets.  ORD: the prologue's load order (layer_body.h ORD); the fused-exchange variant
+// keeps the parent order
 template <int R, int NW, int P, int E, int ROLE, bool MULTI, bool EARLY, int PE = 0, bool W8 = false, int WT = 0,
-          int RW = 0, bool TO = false>
+          int RW = 0, bool TO = false, int ORD = 0>
 void launch_cfg(dim3 grid, size_t lds, const LayerGemv& a, hipStream_t s) {
   const dim3 block(NW * 64 + (role_help(ROLE) ? E * 64 : 0));
   if (a.px) {  // the fused-exchange variant (tensor-parallel ranks)
@@ -77,12 +78,12 @@ void launch_cfg(dim3 grid, size_t lds, const LayerGemv& a, hipStream_t s) {
   }
   KernelTiming& kt = kernel_timing();
   if (kt.start) {
-    hipExtLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW, false, TO>), grid, block,
+    hipExtLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW, false, TO, ORD>), grid, block,
                           (uint32_t)lds, s, kt.start, kt.stop, 0u, a);
     kt = KernelTiming{};
     return;
   }
-  hipLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW, false, TO>), grid, block, lds, s, a);
+  hipLaunchKernelGGL((gemv_q4_0_layer<R, NW, P, E, ROLE, MULTI, EARLY, PE, W8, WT, RW, false, TO, ORD>), grid, block, lds, s, a);
 }
 
 template <int R, int NW, int P, int E, int ROLE, bool EARLY, int PE, int WTA, int WTB>
@@ -110,6 +111,10 @@ struct LayerCfg {
   int rows_max = 0;  // > 0: a tensor-parallel shard entry, for weights of at most this many rows
   int rw = 0;        // > 0: waves carrying rows (layer_body RW), the others only share the prologue
   LaunchFn fn_late = nullptr;  // TO entries: the instance with the tail offsets left to the compiler (LLMI_FFN_TAIL=late)
+  // ORD entries (layer_body.h ORD; LLMI_PRO_ORDER=parent|barrier|split): fn is the parent order, these the
+  // instances with the operand barrier and with the split head issue; ord: the one launched by default
+  LaunchFn fn_bar = nullptr, fn_split = nullptr;
+  int ord = PRO_ORDER_PARENT;
 };
 
 #define LLMI_LCFG(NB, ROLE, R, NW, P, E, MULTI, EARLY, SLAB) \
@@ -134,6 +139,17 @@ struct LayerCfg {
   {NB, ROLE, R, NW, P, E, false, SLAB, false,                                                                 \
    launch_cfg<R, NW, P, E, ROLE, false, false, PE, false, 0, 0, true>, false, 0, nullptr, 0, 0,             \
    launch_cfg<R, NW, P, E, ROLE, false, false, PE>}
+// TO entries and EARLY entries with the ORD instances beside the parent's (SPLIT: the entry's ORD_SPLIT groups)
+#define LLMI_LCFGPTO(NB, ROLE, R, NW, P, E, SLAB, PE, SPLIT, ORD)                                             \
+  {NB, ROLE, R, NW, P, E, false, SLAB, false,                                                                 \
+   launch_cfg<R, NW, P, E, ROLE, false, false, PE, false, 0, 0, true>, false, 0, nullptr, 0, 0,             \
+   launch_cfg<R, NW, P, E, ROLE, false, false, PE>,                                                           \
+   launch_cfg<R, NW, P, E, ROLE, false, false, PE, false, 0, 0, true, ORD_BAR>,                               \
+   launch_cfg<R, NW, P, E, ROLE, false, false, PE, false, 0, 0, true, SPLIT>, ORD}
+#define LLMI_LCFGEO(NB, ROLE, R, NW, P, E, SLAB, SPLIT, ORD)                                                  \
+  {NB, ROLE, R, NW, P, E, false, SLAB, false, launch_cfg<R, NW, P, E, ROLE, false, true>, false, 0, nullptr, 0, 0, \
+   nullptr, launch_cfg<R, NW, P, E, ROLE, false, true, 0, false, 0, 0, false, ORD_BAR>,                       \
+   launch_cfg<R, NW, P, E, ROLE, false, true, 0, false, 0, 0, false, SPLIT>, ORD}
 // Q8_0 weights: row-major, single chunk (P passes of 16-B half blocks)
 // kq entries, one per weight type (+ the q|k Q4_K, v Q6_K launch for qkv roles)
 #define LLMI_LCFGK1(NB, ROLE, R, NW, P, E, EARLY, PE, WT, SLAB)                                        \
@@ -159,6 +175,28 @@ struct LayerCfg {
 // 4B down 5.8 -> 5.4 us with PE3 (of 5) instead of EARLY; 27B
 // gate_up 35.8 -> 26.3 us with R8 NW8 P4 slab, qkv 10.4 -> 10.0 us, down
 // 24 -> 17-19.5 us issuing the weights after the quantized x is in LDS)
+// The 4B entries' prologue order (layer_body.h ORD): the split groups (sweepable at build time) and the order
+// launched by default (LLMI_PRO_ORDER overrides it).  Decided in the decode graph, one box, three interleaved
+// bench.py pairs per variant against the parent's library (955.6-957.1 tok/s over 12 runs), one entry changed at a
+// time (profiles/r17_prologue_order.txt):
+//   gate_up split 2/2/3 972.5-973.7 (+1.7 %; 1/3/3, 2/1/4, 2/3/2 within 1 tok/s of it, 3/2/2 971.3-971.8), standalone
+//     10.4 -> 9.9 us; the barrier alone is slower standalone (10.6 us): it is not what helps here;
+//   down split 1/2/0 966.1-966.9 (+1.1 %; 1/1/1 and 2/1/0 the same within 1 tok/s), standalone 6.29 vs 6.26 us --
+//     equal standalone, a gain in the graph, as the tail offsets were;
+//   qkv (k_attn.hip's block instance, layer_body.h LLMI_QKV_ORDER) barrier 958.3-958.5 (+0.2 %), split 3/2/0 954.1-954.3;
+//   all three together 985.6-985.9 (+3.1 %), without the qkv barrier 983.0-983.4.
+#ifndef LLMI_GU_SPLIT
+#define LLMI_GU_SPLIT ORD_SPLIT(2, 2)  // gate_up head of 7 passes: 2 / 2 / 3
+#endif
+#ifndef LLMI_DOWN_SPLIT
+#define LLMI_DOWN_SPLIT ORD_SPLIT(1, 2)  // down head of 3 passes: 1 / 2 / 0
+#endif
+#ifndef LLMI_GU_ORDER
+#define LLMI_GU_ORDER PRO_ORDER_SPLIT
+#endif
+#ifndef LLMI_DOWN_ORDER
+#define LLMI_DOWN_ORDER PRO_ORDER_SPLIT
+#endif
 #ifndef KQ_GU_SLAB
 #define KQ_GU_SLAB 1
 #endif
@@ -175,14 +213,14 @@ const LayerCfg kLayerCfgs[] = {
     LLMI_LCFG(168, ROLE_PLAIN, 8, 4, 7, 2, true, true, 0),     // 27B qkv l0  8192 rows -> 256 WGs
     // PRO: residual + norm prologue
     LLMI_LCFG(36, ROLE_PRO, 8, 2, 5, 9, false, true, 0),       // 1B qkv      96 WGs
-    LLMI_LCFG(80, ROLE_PRO, 4, 4, 5, 10, false, true, 0),      // 4B qkv      256 WGs
+    LLMI_LCFGEO(80, ROLE_PRO, 4, 4, 5, 10, 0, LLMI_QKV_SPLIT, LLMI_QKV_ORDER),  // 4B qkv      256 WGs
     LLMI_LCFG(120, ROLE_PRO, 8, 4, 8, 15, true, true, 0),      // 12B qkv     256 WGs
     LLMI_LCFGW(168, ROLE_PRO, 4, 8, 6, 11, true, true, 1, 1024),  // 27B qkv shard (tp 8): 1 row wave -> 256 WGs
     LLMI_LCFGW(168, ROLE_PRO, 4, 8, 6, 11, true, true, 2, 2048),  // 27B qkv shard (tp 4): 2 row waves -> 256 WGs
     LLMI_LCFG(168, ROLE_PRO, 4, 8, 6, 11, true, true, 0),      // 27B qkv     256 WGs
     // GELU: prologue + GELU epilogue, 2H = R NW interleaved gate/up rows per WG
     LLMI_LCFGP(36, ROLE_GELU, 8, 8, 5, 3, 0, 3),              // 1B  13824 rows, H 32 -> 216 WGs (PE3: 5.9 -> 5.1 us)
-    LLMI_LCFGPT(80, ROLE_GELU, 8, 10, 10, 4, 1, 7),           // 4B  20480 rows, H 40 -> 256 WGs (PE7: 8.4 -> 7.8 us)
+    LLMI_LCFGPTO(80, ROLE_GELU, 8, 10, 10, 4, 1, 7, LLMI_GU_SPLIT, LLMI_GU_ORDER),  // 4B  20480 rows, H 40 -> 256 WGs (PE7: 8.4 -> 7.8 us)
     LLMI_LCFG(120, ROLE_GELU, 8, 8, 8, 8, true, false, 0),     // 12B 30720 rows, H 32 -> 480 WGs
     // (a 27B gate_up shard entry with longer weight chunks -- P 7 or 11 instead of 4, more bytes in flight per
     // work-group of the tp-8 rank's 84; P does not change a row's pass order: 2.12-2.13 vs 2.08 ms per rank token,
@@ -198,7 +236,7 @@ const LayerCfg kLayerCfgs[] = {
     LLMI_LCFG(216, ROLE_QUANT, 1, 4, 4, 4, false, true, 0),    // 1B down     1152 rows -> 288 WGs (6.5 -> 5.0 us)
     // (a 4B QUANT shard entry, NW 2: 0.948 vs 0.907 ms per tp-8 rank -- 160 work-groups each quantizing the
     // whole 40 KB hid; not kept)
-    LLMI_LCFGPT(320, ROLE_QUANT, 1, 10, 5, 2, 0, 3),          // 4B down     2560 rows -> 256 WGs (PE3: 5.8 -> 5.4 us)
+    LLMI_LCFGPTO(320, ROLE_QUANT, 1, 10, 5, 2, 0, 3, LLMI_DOWN_SPLIT, LLMI_DOWN_ORDER),  // 4B down     2560 rows -> 256 WGs (PE3: 5.8 -> 5.4 us)
     LLMI_LCFG(480, ROLE_QUANT, 1, 8, 8, 4, false, true, 0),    // 12B down    3840 rows -> 480 WGs
     LLMI_LCFG(672, ROLE_QUANT, 1, 8, 6, 6, true, false, 0),    // 27B down    5376 rows -> 672 WGs
     // Q8_0 weights (Gemma-3 1B Q8_0, BASELINE configs[3]): 2 nb half-block units per row
@@ -300,7 +338,14 @@ int launch_layer_gemv(const DevWeight& w, LayerGemv a, int role, hipStream_t s) 
   // LLMI_FFN_TAIL=late: the launch as it was before the tail offsets were fixed early (A/B runs, and the test that
   // holds the two to the same bits)
   const char* tail = c.fn_late ? getenv("LLMI_FFN_TAIL") : nullptr;
-  (tail && !strcmp(tail, "late") ? c.fn_late : c.fn)(dim3(nwg), lds, a, s);
+  LaunchFn fn = c.fn;
+  if (tail && !strcmp(tail, "late")) {
+    fn = c.fn_late;
+  } else if (c.fn_bar) {  // LLMI_PRO_ORDER: the prologue's load order (A/B runs, and the test that holds them to the same bits)
+    const int o = pro_order(c.ord);
+    fn = o == PRO_ORDER_SPLIT ? c.fn_split : o == PRO_ORDER_BARRIER ? c.fn_bar : c.fn;
+  }
+  fn(dim3(nwg), lds, a, s);
   LLMI_HIP(hipGetLastError());
   return nwg;
 }

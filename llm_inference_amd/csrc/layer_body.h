@@ -139,6 +139,18 @@ __device__ __forceinline__ void load_chunk_rb_tail(Chunk<P>& c, __amdgpu_buffer_
   }
 }
 
+// passes [PA, PB) of a chunk from offsets fixed by tail_offsets<P, P0> (ORD split groups: P0 <= PA)
+template <int P, int P0, int PA, int PB>
+__device__ __forceinline__ void load_chunk_rb_pinned(Chunk<P>& c, __amdgpu_buffer_rsrc_t rq, __amdgpu_buffer_rsrc_t rd,
+                                                     const TailOff<P, P0>& o) {
+  static_assert(P0 <= PA && PB <= P, "pinned passes");
+#pragma unroll
+  for (int p = PA; p < PB; p++) {
+    c.q[p] = buf_ld16(rq, o.q[p - P0], 0);
+    c.sw[p] = buf_ld2(rd, o.d[p - P0], 0);
+  }
+}
+
 // Q8_0 weights (W8): a lane's 16-B unit is HALF a block (unit u = block
 // u / 2, elements 16 (u % 2) ..; L is even, so the half is lane-fixed: j % 2),
 // dotted with the matching half of the activation block; no zero point
@@ -292,7 +304,11 @@ __device__ __forceinline__ float rb_row_sums(float v, float (&tot)[R <= 2 ? R : 
 //   0 start, 1 first weight passes issued, 2 prologue operands landed (QUANT: x quantized), 3 x complete in LDS
 //   (past the barrier), 4 last weight pass issued, 5 last pass consumed, 6 epilogue stores issued, 7 end,
 //   8 / 9 the prologue's first / second reduction done; 10 the wave's HW_ID, 11 its XCC_ID (read once at start)
-constexpr int LAYER_TRACE_W = 16;
+// and by lane 0 of EVERY wave w (LAYER_MARK_W / LAYER_MARK_WD, at most LAYER_TRACE_NW waves):
+//   16 + w the wave's prologue operands landed (PRO / GELU: its `ss` loop done, the stamp ordered after the sum;
+//   QUANT: its x blocks quantized), 32 + w the wave's last head pass issued
+constexpr int LAYER_TRACE_W = 48;
+constexpr int LAYER_TRACE_NW = 16;
 __device__ unsigned long long* g_layer_trace = nullptr;
 #define LAYER_MARK(ph)                                                                                                 \
   do {                                                                                                                 \
@@ -305,9 +321,25 @@ __device__ unsigned long long* g_layer_trace = nullptr;
       g_layer_trace[(size_t)blockIdx.x * LAYER_TRACE_W + 11] = __builtin_amdgcn_s_getreg((31 << 11) | 20); \
     }                                                                                                       \
   } while (0)
+#define LAYER_MARK_W(base)                                                                                    \
+  do {                                                                                                        \
+    if (g_layer_trace && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) < LAYER_TRACE_NW)                      \
+      g_layer_trace[(size_t)blockIdx.x * LAYER_TRACE_W + (base) + (threadIdx.x >> 6)] = wall_clock64();       \
+  } while (0)
+#define LAYER_MARK_WD(base, dep)        \
+  do {                                  \
+    asm volatile("" ::"v"(dep));        \
+    LAYER_MARK_W(base);                 \
+  } while (0)
 #else
 #define LAYER_MARK(ph) \
   do {                 \
+  } while (0)
+#define LAYER_MARK_W(base) \
+  do {                     \
+  } while (0)
+#define LAYER_MARK_WD(base, dep) \
+  do {                           \
   } while (0)
 #define LAYER_MARK_ID() \
   do {                  \
@@ -394,8 +426,39 @@ constexpr int HELP_K4 = 6;  // float4 per helper lane and operand: n <= E * 256 
 // row-major weights only).
 // PXF: the fused-exchange code (a.px_in / a.px_out honoured); false compiles it out (the one-device launches)
 // TO (PE entries of Q4_0 / Q8_0 weights): the tail passes' offsets are fixed before the head is issued (tail_offsets)
+// ORD (PRO / GELU / QUANT, single-chunk row-bound Q4_0 / Q8_0, not the helper roles): where the prologue's operand
+// loads and the head issue (EARLY: all P passes, else the PE head passes) stand in program order.  No operand,
+// summation or rounding moves: rows are those of ORD 0 bit for bit.
+//   0         the operands, then the whole head, then the prologue's steps;
+//   ORD_BAR   one raw s_barrier (no vmcnt wait) between the operand loads and the head: EVERY wave's operand loads
+//             enter the CU's in-order vector-memory queue ahead of every wave's weight loads (as the helper roles do);
+//   ORD_SPLIT(GA, GB)  the barrier, and the head issued in groups between the prologue's steps, so a wave is not
+//             held at the issue of the whole head before work whose operands have landed: GA passes, the `ss` loop
+//             and reduction #1 (QUANT: the first round's blocks), GB passes, the residual update and reduction #2
+//             (QUANT: the other rounds), the head's other passes, the quantization.  The offsets of every pass after
+//             group A are fixed ahead of it (tail_offsets), so no group's address arithmetic waits on earlier loads.
+constexpr int ORD_BAR = 1;
+constexpr int ORD_SPLIT(int ga, int gb) { return 16 * ga + gb; }  // ga >= 1
+// The order a table entry launches (k_layer.hip kLayerCfgs, k_attn.hip kBlockCfgs): the entry's default, or
+// LLMI_PRO_ORDER=parent|barrier|split for every entry that has the instances
+enum { PRO_ORDER_PARENT = 0, PRO_ORDER_BARRIER = 1, PRO_ORDER_SPLIT = 2 };
+inline int pro_order(int dflt) {
+  const char* e = getenv("LLMI_PRO_ORDER");
+  if (!e || !*e) return dflt;
+  if (!strcmp(e, "parent")) return PRO_ORDER_PARENT;
+  if (!strcmp(e, "barrier")) return PRO_ORDER_BARRIER;
+  if (!strcmp(e, "split")) return PRO_ORDER_SPLIT;
+  throw std::runtime_error("LLMI_PRO_ORDER: parent, barrier or split");
+}
+// the 4B qkv role (standalone launch and the attention block's instance): all 5 passes are its head
+#ifndef LLMI_QKV_SPLIT
+#define LLMI_QKV_SPLIT ORD_SPLIT(2, 2)  // 2 / 2 / 1
+#endif
+#ifndef LLMI_QKV_ORDER
+#define LLMI_QKV_ORDER PRO_ORDER_BARRIER  // (the split costs the block 0.3 %: k_layer.hip's note on the orders)
+#endif
 template <int R, int NW, int P, int E, int ROLE, bool MULTI, bool EARLY, int SYNC = 0, int PE = 0, bool W8 = false,
-          int WT = 0, int RW0 = 0, bool PXF = false, bool TO = false>
+          int WT = 0, int RW0 = 0, bool PXF = false, bool TO = false, int ORD = 0>
 __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, unsigned char* s_dyn,
                                            const BlockSync& bs) {
   constexpr bool HELP = role_help(ROLE);
@@ -409,6 +472,13 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
   static_assert(WT == 0 || (RB && R <= 8 && !MULTI && !HELP && !W8), "kq: single-chunk row-bound lanes");
   static_assert(!(PXF && HELP), "fused exchange: not in the helper roles (their LDS words are ordered differently)");
   static_assert(!TO || (PE > 0 && WT == 0), "TO: PE entries, not the kq layout");
+  constexpr bool OB = ORD != 0, SPLIT = ORD >= 16;
+  constexpr int HEAD = EARLY ? P : PE;                 // passes issued during the prologue
+  constexpr int GA = SPLIT ? ORD / 16 : HEAD, GB = SPLIT ? ORD % 16 : 0;  // split groups; group C = HEAD - GA - GB
+  static_assert(!OB || ((ROLE == ROLE_PRO || ROLE == ROLE_GELU || ROLE == ROLE_QUANT) && RB && !MULTI && WT == 0 &&
+                        !PXF && SYNC != SYNC_WAIT && HEAD > 0),
+                "ORD: single-chunk row-bound PRO / GELU / QUANT roles of Q4_0 / Q8_0 weights");
+  static_assert(!SPLIT || GA + GB <= HEAD, "ORD_SPLIT: groups within the head");
   LAYER_MARK(0);
   LAYER_MARK_ID();
   BLK_MARK(bs, 0);
@@ -547,14 +617,30 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
       if constexpr (MULTI) load_chunk<P>(cb, qw, dw, 64 * P, total, lane);
     }
   };
-  TailOff<P, PE> toff;
-  auto issue_head = [&]() {  // passes [0, PE)
-    if constexpr (TO) tail_offsets<P, PE>(toff, voq, vod, sq, sd, npass);
-    if constexpr (PE > 0 && WT != 0) load_chunk_kq<P, WT, 0, PE>(ca, rq, rd, kq, voq, vod, sq, sd, 0, npass);
+  constexpr int PIN0 = SPLIT ? GA : PE;  // first pass whose offsets are fixed ahead
+  TailOff<P, PIN0> toff;
+  auto issue_head = [&]() {  // passes [0, PE); SPLIT: group A
+    if constexpr (TO || SPLIT) tail_offsets<P, PIN0>(toff, voq, vod, sq, sd, npass);
+    if constexpr (SPLIT) load_chunk_rb_part<R, P, 0, GA>(ca, rq, rd, voq, vod, sq, sd, npass);
+    else if constexpr (PE > 0 && WT != 0) load_chunk_kq<P, WT, 0, PE>(ca, rq, rd, kq, voq, vod, sq, sd, 0, npass);
     else if constexpr (PE > 0) load_chunk_rb_part<R, P, 0, PE>(ca, rq, rd, voq, vod, sq, sd, npass);
   };
+  auto issue_group_b = [&]() {  // SPLIT: passes [GA, GA + GB), held in place
+    if constexpr (SPLIT && GB > 0) {
+      load_chunk_rb_pinned<P, PIN0, GA, GA + GB>(ca, rq, rd, toff);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto issue_group_c = [&]() {  // SPLIT: the head's other passes
+    if constexpr (SPLIT && GA + GB < HEAD) {
+      load_chunk_rb_pinned<P, PIN0, GA + GB, HEAD>(ca, rq, rd, toff);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (SPLIT) LAYER_MARK_W(32);
+  };
   auto issue_tail = [&]() {  // passes [PE, P), or everything
-    if constexpr (TO) load_chunk_rb_tail<P, PE>(ca, rq, rd, toff);
+    if constexpr (SPLIT) load_chunk_rb_pinned<P, PIN0, HEAD, P>(ca, rq, rd, toff);
+    else if constexpr (TO) load_chunk_rb_tail<P, PE>(ca, rq, rd, toff);
     else if constexpr (PE > 0 && WT != 0) load_chunk_kq<P, WT, PE, P>(ca, rq, rd, kq, voq, vod, sq, sd, 0, npass);
     else if constexpr (PE > 0) load_chunk_rb_part<R, P, PE, P>(ca, rq, rd, voq, vod, sq, sd, npass);
     else issue_weights();
@@ -683,8 +769,11 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
         n4[k][h] = buf_ldf4(rn, off + 16 * h);
       }
     }
-    if constexpr (EARLY) issue_weights();
+    if constexpr (OB) __builtin_amdgcn_s_barrier();  // (no vmcnt wait: the loads are only ordered, see ORD)
+    if constexpr (EARLY && !SPLIT) issue_weights();
     else issue_head();
+    if constexpr (SPLIT) __builtin_amdgcn_sched_barrier(0);
+    else LAYER_MARK_W(32);
     LAYER_MARK(1);
     if (yfx) {  // (the weights' first passes are in flight while the peers' words arrive)
 #pragma unroll
@@ -711,10 +800,12 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
       }
     }
     LAYER_MARK(2);
+    LAYER_MARK_WD(16, ss);
     BLK_MARK(bs, 5);
     const float sc1 = rms_scale_d(wg_sum<NW>(ss, s_red[0]), n, a.eps);
     LAYER_MARK(8);
     BLK_MARK(bs, 6);
+    issue_group_b();
     float ss2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < EB; k++) {
@@ -745,6 +836,7 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
     const float sc2 = rms_scale_d(wg_sum<NW>(ss2, s_red[1]), n, a.eps);
     LAYER_MARK(9);
     BLK_MARK(bs, 7);
+    issue_group_c();
 #pragma unroll
     for (int k = 0; k < EB; k++) {
       float v[8];
@@ -779,8 +871,11 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
         xr[r][1] = yb[2 * i + 1];
       }
     }
-    if constexpr (EARLY) issue_weights();
+    if constexpr (OB) __builtin_amdgcn_s_barrier();  // (no vmcnt wait: the loads are only ordered, see ORD)
+    if constexpr (EARLY && !SPLIT) issue_weights();
     else issue_head();
+    if constexpr (SPLIT) __builtin_amdgcn_sched_barrier(0);
+    else LAYER_MARK_W(32);
     LAYER_MARK(1);
     if (fin) {  // fused exchange: from this rank's mailbox, the weights' first passes in flight
 #pragma unroll
@@ -802,8 +897,14 @@ __device__ __forceinline__ void layer_body(const LayerGemv& a, const int bid, un
           else q8_block_quad(v, i & 3, s_x + (i >> 2));
         }
       }
+      if constexpr (SPLIT) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (r == 0) issue_group_b();
+      }
     }
+    issue_group_c();
     LAYER_MARK(2);
+    LAYER_MARK_W(16);
   } else {
     // x blocks -> LDS: clamped unconditional loads (no branch between them
     // and the weight loads, so the stores wait only for their own data)

@@ -6,18 +6,23 @@
     python scripts/ffn_trace.py dir/4b.gate_up.gelu_late.bin dir/4b.gate_up.gelu.bin ...
 
 Each file holds one launch (the last of 24 back to back, every one reading another copy of the weight from HBM):
-[work-group][16] 64-bit words, layer_body.h LAYER_MARK -- wall clocks (100 MHz) of
+[work-group][48] 64-bit words, layer_body.h LAYER_MARK -- wall clocks (100 MHz) of
   0 start, 1 first weight passes issued, 2 prologue operands landed (down: x quantized), 3 x complete in LDS,
   4 last weight pass issued, 5 last pass consumed, 6 epilogue stores issued, 7 end,
-  8 / 9 the prologue's first / second reduction done (gate_up only); word 10 HW_ID, word 11 XCC_ID of wave 0.
+  8 / 9 the prologue's first / second reduction done (gate_up only); word 10 HW_ID, word 11 XCC_ID of wave 0;
+  and per wave w (lane 0 of every wave): word 16 + w the wave's prologue operands landed (its `ss` loop done;
+  down: its x blocks quantized), word 32 + w the wave's last head pass issued.
 The FFN launches read no position-dependent operand: the trace at position 537 is the trace at any position.
-Times are us from the first work-group's start; stamps are thread 0's (wave 0 of each work-group).
+Times are us from the first work-group's start; the phase stamps are thread 0's (wave 0 of each work-group), the
+per-wave lines give min / mean / max over all waves of all work-groups and the mean over work-groups of a
+work-group's last wave (what its next barrier waits for).
 """
 import sys
 
 import numpy as np
 
-W = 16
+W, NWMAX = 48, 16
+PER_WAVE = [(16, "operands landed"), (32, "head issue done")]
 PHASES = [(0, "start"), (1, "first passes issued"), (2, "prologue operands landed"), (8, "first reduction done"),
           (9, "second reduction done"), (3, "x complete (barrier)"), (4, "last pass issued"), (5, "last pass consumed"),
           (6, "epilogue stores issued"), (7, "end")]
@@ -40,6 +45,13 @@ def summarise(path):
             print(f"  {name:26s} {np.nanmean(rel[:, k]):7.2f} {np.nanmax(rel[:, k]):7.2f}")
     dur = rel[:, 7] - rel[:, 0]
     print(f"  work-group start -> end    {dur.mean():7.2f} {dur.max():7.2f}")
+    for base, name in PER_WAVE:
+        pw = raw[:, base:base + NWMAX].astype(np.float64)
+        pw = np.where(pw > 0, (pw - t0) / 100.0, np.nan)
+        if np.isfinite(pw).any():
+            print(f"  per wave, {name:17s} min {np.nanmin(pw):5.2f} mean {np.nanmean(pw):5.2f} max {np.nanmax(pw):5.2f}; "
+                  f"a work-group's last wave, mean {np.nanmean(np.nanmax(pw, axis=1)):5.2f}; "
+                  f"spread inside a work-group, mean {np.nanmean(np.nanmax(pw, axis=1) - np.nanmin(pw, axis=1)):5.2f}")
     for a, b, name in ((0, 1, "issue of the first passes"), (3, 4, "x complete -> last issued"),
                        (4, 5, "last issued -> consumed"), (5, 7, "consumed -> end")):
         d = rel[:, b] - rel[:, a]

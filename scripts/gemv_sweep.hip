@@ -227,6 +227,18 @@ int main(int argc, char** argv) {
       timeit("layer pro+gelu (again)", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
     if (layer_gemv_supported(probe, LAYER_QUANT))
       timeit("layer quant (again)", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+    // the prologue orders of the 4B qkv / gate_up / down entries (LLMI_PRO_ORDER; layer_body.h ORD), same session
+    for (const char* ord : {"parent", "barrier", "split", "parent"}) {
+      setenv("LLMI_PRO_ORDER", ord, 1);
+      const std::string tag = std::string(" (order ") + ord + ")";
+      if (nb == 80 && layer_gemv_supported(probe, LAYER_PRO))
+        timeit(("layer pro" + tag).c_str(), [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_PRO), pro, LAYER_PRO, s); });
+      if (nb == 80 && layer_gemv_supported(probe, LAYER_GELU))
+        timeit(("layer pro+gelu" + tag).c_str(), [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
+      if (nb == 320 && layer_gemv_supported(probe, LAYER_QUANT))
+        timeit(("layer quant" + tag).c_str(), [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+    }
+    unsetenv("LLMI_PRO_ORDER");
     // MALL experiment: a default-policy prefetch of the same weight right
     // before the GEMV (as a forked graph branch would do during attention)
     {
@@ -294,6 +306,14 @@ int main(int argc, char** argv) {
       unsetenv("LLMI_FFN_TAIL");
       if (layer_gemv_supported(probe, LAYER_GELU)) trace("gelu", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
       if (layer_gemv_supported(probe, LAYER_QUANT)) trace("quant", [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+      // the prologue orders (LLMI_PRO_ORDER) of the 4B entries: per-wave stamps in words 16.. / 32.. (ffn_trace.py)
+      for (const char* ord : {"parent", "barrier", "split"}) {
+        setenv("LLMI_PRO_ORDER", ord, 1);
+        if (nb == 80 && layer_gemv_supported(probe, LAYER_PRO)) trace((std::string("pro_") + ord).c_str(), [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_PRO), pro, LAYER_PRO, s); });
+        if (nb == 80 && layer_gemv_supported(probe, LAYER_GELU)) trace((std::string("gelu_") + ord).c_str(), [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_GELU), gl, LAYER_GELU, s); });
+        if (nb == 320 && layer_gemv_supported(probe, LAYER_QUANT)) trace((std::string("quant_") + ord).c_str(), [&](const DevWeight& w) { launch_layer_gemv(lw(w, LAYER_QUANT), qz, LAYER_QUANT, s); });
+      }
+      unsetenv("LLMI_PRO_ORDER");
       (void)hipFree(tr);
     }
 #endif
@@ -378,6 +398,16 @@ int main(int argc, char** argv) {
       geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true>, 80, 640, gs, true);
       geo_role("SLAB gelu R8 NW10 P10 E4 PE8 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 8, false, 0, 0, false, true>, 80, 640, gs, true);
       geo_role("SLAB gelu R8 NW10 P10 E4 PE9 TO", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 9, false, 0, 0, false, true>, 80, 640, gs, true);
+      // prologue order (ORD): the operand barrier, and the head of 7 split 2/2/3, 3/2/2, 2/3/2, 1/3/3
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO barrier", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true, ORD_BAR>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO 2/2/3", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true, ORD_SPLIT(2, 2)>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO 3/2/2", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true, ORD_SPLIT(3, 2)>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO 2/3/2", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true, ORD_SPLIT(2, 3)>, 80, 640, gs, true);
+      geo_role("SLAB gelu R8 NW10 P10 E4 PE7 TO 1/3/3", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false, 7, false, 0, 0, false, true, ORD_SPLIT(1, 3)>, 80, 640, gs, true);
+      geo_role("pro R4 NW4 P5 E10 barrier", gemv_q4_0_layer<4, 4, 5, 10, 1, false, true, 0, false, 0, 0, false, false, ORD_BAR>, 16, 256, pro, true);
+      geo_role("pro R4 NW4 P5 E10 2/2/1", gemv_q4_0_layer<4, 4, 5, 10, 1, false, true, 0, false, 0, 0, false, false, ORD_SPLIT(2, 2)>, 16, 256, pro, true);
+      geo_role("pro R4 NW4 P5 E10 1/2/2", gemv_q4_0_layer<4, 4, 5, 10, 1, false, true, 0, false, 0, 0, false, false, ORD_SPLIT(1, 2)>, 16, 256, pro, true);
+      geo_role("pro R4 NW4 P5 E10 3/2/0", gemv_q4_0_layer<4, 4, 5, 10, 1, false, true, 0, false, 0, 0, false, false, ORD_SPLIT(3, 2)>, 16, 256, pro, true);
       geo_role("gelu R5 NW16 P7 E3 (table, flat)", gemv_q4_0_layer<5, 16, 7, 3, 2, false, false>, 80, 1024, gl, true);
       geo_role("gelu R8 NW10 P10 E4", gemv_q4_0_layer<8, 10, 10, 4, 2, false, false>, 80, 640, gl, true);
       geo_role("gelu R8 NW10 P10 E4 early", gemv_q4_0_layer<8, 10, 10, 4, 2, false, true>, 80, 640, gl, true);
@@ -450,6 +480,11 @@ int main(int argc, char** argv) {
       geo_role("quant R1 NW10 P5 E2 PE2 TO", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 2, false, 0, 0, false, true>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 PE3 TO", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 3, false, 0, 0, false, true>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 PE4 TO", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 4, false, 0, 0, false, true>, 10, 640, qz, false);
+      // prologue order (ORD): the operand barrier, and the head of 3 split 1/1/1, 1/2/0, 2/1/0
+      geo_role("quant R1 NW10 P5 E2 PE3 TO barrier", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 3, false, 0, 0, false, true, ORD_BAR>, 10, 640, qz, false);
+      geo_role("quant R1 NW10 P5 E2 PE3 TO 1/1/1", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 3, false, 0, 0, false, true, ORD_SPLIT(1, 1)>, 10, 640, qz, false);
+      geo_role("quant R1 NW10 P5 E2 PE3 TO 1/2/0", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 3, false, 0, 0, false, true, ORD_SPLIT(1, 2)>, 10, 640, qz, false);
+      geo_role("quant R1 NW10 P5 E2 PE3 TO 2/1/0", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 3, false, 0, 0, false, true, ORD_SPLIT(2, 1)>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 (table)", gemv_q4_0_layer<1, 10, 5, 2, 3, false, true>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 late", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false>, 10, 640, qz, false);
       geo_role("quant R1 NW10 P5 E2 PE1", gemv_q4_0_layer<1, 10, 5, 2, 3, false, false, 1>, 10, 640, qz, false);
