@@ -445,6 +445,24 @@ int llmi_gemm_rows_f16(const void* w_blocks, int n_rows, int n_cols, const uint1
  * not supported.  (LLMI_PG_SKINNY=0: never 1.) */
 int llmi_gemm_rows_plan(int n_rows, int n_cols, int T);
 
+/* op level, host pointers, synchronous: out[t][n] = sum_b d_w[n][b] d_x[t][b] isum[t][n][b], the int8 GEMM of the
+ * batch steps on Q8_0 layers, of the int8 path and of the last layer's detour.  wtype: 8
+ * (Q8_0, 34-B blocks) or 2 (Q4_0, 18-B blocks); w_blocks in GGUF form [n_rows][n_cols / 32]; x: [T][n_cols] f32,
+ * quantized on the device to Q8_0 blocks exactly as llmi_quantize_row_q8_0 does; out: [T][ostride] f32, ostride >=
+ * n_rows -- only out[t][0 .. n_rows) of the T rows is written.  kernel: 0 = the session's choice
+ * (llmi_gemm_rows_i8_plan), 1 = the skinny kernel (T <= 32), 2 = the tiled kernel (v5); 1 and 2 write the same bits.
+ * slab: 1 = the Q4_0 weight is repacked slab-major as the session's layer weights are (n_cols % 256 == 0).
+ * Errors: NULL pointers, kernel outside 0..2, slab outside 0..1: LLMI_E_ARG; wtype: LLMI_E_TYPE; T outside
+ * 1..LLMI_BATCH_TOKENS_MAX, or kernel 1 with T > 32: LLMI_E_RANGE; n_rows % 32 != 0, n_cols % 128 != 0, slab with
+ * Q8_0 or n_cols % 256 != 0, ostride < n_rows: LLMI_E_SIZE. */
+int llmi_gemm_rows_i8(const void* w_blocks, uint32_t wtype, int n_rows, int n_cols, const float* x, int T, int kernel,
+                      int slab, float* out, int ostride);
+/* no GPU work: the kernel llmi_gemm_rows_i8(kernel = 0) and the session run for a weight of wtype [n_rows][n_cols]
+ * at T token rows: 1 = skinny, 5 = the tiled kernel v5; 0: the type or shape is not supported.  The skinny kernel
+ * measured behind v5 at every row count, so the plan is 5 unless LLMI_GR_I8_T=<rows> moves
+ * the switch for a comparison.  (LLMI_PG_SKINNY=0 or a forced v5 geometry, LLMI_PG5: never 1.) */
+int llmi_gemm_rows_i8_plan(uint32_t wtype, int n_rows, int n_cols, int T);
+
 /* Enqueue n_steps decode steps without waiting (bench); llmi_session_sync
  * waits and copies the produced tokens (may be NULL). */
 int llmi_session_enqueue(llmi_session* s, int32_t first, int pos, int n_steps);

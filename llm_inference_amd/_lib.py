@@ -145,6 +145,8 @@ _SIGS = {
     "llmi_logits_rows_rb": (C.c_int, [C.c_int]),
     "llmi_gemm_rows_f16": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "llmi_gemm_rows_plan": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "llmi_gemm_rows_i8": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),
+    "llmi_gemm_rows_i8_plan": (C.c_int, [C.c_uint32, C.c_int, C.c_int, C.c_int]),
     "llmi_score_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp]),
     "llmi_score_rows_top": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp, _vp, _vp, _vp, C.c_int, _vp,
                                       _vp]),

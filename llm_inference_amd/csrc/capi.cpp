@@ -740,6 +740,56 @@ int llmi_gemm_rows_f16(const void* w_blocks, int n_rows, int n_cols, const uint1
   });
 }
 
+int llmi_gemm_rows_i8_plan(uint32_t wtype, int n_rows, int n_cols, int T) {
+  if (n_rows <= 0 || n_cols <= 0 || n_cols % 32 || T < 1) return 0;
+  return prefill_gemm_plan(wtype, n_rows, n_cols, 0, T);
+}
+
+int llmi_gemm_rows_i8(const void* w_blocks, uint32_t wtype, int n_rows, int n_cols, const float* x, int T, int kernel,
+                      int slab, float* out, int ostride) {
+  return guard([&] {
+    if (!w_blocks || !x || !out) throw status_error(LLMI_E_ARG, "gemm_rows_i8: null pointer");
+    if (kernel < 0 || kernel > 2) throw status_error(LLMI_E_ARG, "gemm_rows_i8: kernel must be 0, 1 or 2 (kernel)");
+    if (slab < 0 || slab > 1) throw status_error(LLMI_E_ARG, "gemm_rows_i8: slab must be 0 or 1 (slab)");
+    if (wtype != T_Q8_0 && wtype != T_Q4_0)
+      throw status_error(LLMI_E_TYPE, "gemm_rows_i8: Q8_0 or Q4_0 weights, not tensor type " + std::to_string(wtype) + " (wtype)");
+    if (T < 1 || T > LLMI_BATCH_TOKENS_MAX)
+      throw status_error(LLMI_E_RANGE, "gemm_rows_i8: T must be in 1.." + std::to_string(LLMI_BATCH_TOKENS_MAX) + " (T)");
+    if (kernel == 1 && T > GEMM_ROWS_I8_T_MAX)
+      throw status_error(LLMI_E_RANGE, "gemm_rows_i8: the skinny kernel takes T <= " + std::to_string(GEMM_ROWS_I8_T_MAX) + " (T)");
+    if (n_rows <= 0 || n_rows % 32 || n_cols <= 0 || n_cols % 128)
+      throw status_error(LLMI_E_SIZE, "gemm_rows_i8: n_rows must be a multiple of 32, n_cols of 128");
+    if (slab && (wtype != T_Q4_0 || n_cols % 256))
+      throw status_error(LLMI_E_SIZE, "gemm_rows_i8: the slab layout needs Q4_0 weights and n_cols % 256 == 0");
+    if (ostride < n_rows) throw status_error(LLMI_E_SIZE, "gemm_rows_i8: ostride < n_rows");
+    Ctx& c = ctx();
+    DevWeight w = alloc_weight(wtype, n_rows, n_cols);
+    try {
+      upload_rows(w, 0, w_blocks, n_rows, c.stream);
+      if (slab) to_slab_layout(w, c.stream);
+      if (!prefill_gemm_supported(w)) throw status_error(LLMI_E_SIZE, "gemm_rows_i8: unsupported shape");
+      const int nb = n_cols / 32;
+      const size_t xb = (size_t)T * n_cols * 4, ob = (size_t)T * ostride * 4;
+      float* xd = (float*)c.get(0, xb);
+      float* od = (float*)c.get(1, ob);
+      Q8Act q;  // the T rows' Q8_0 blocks, row after row
+      q.xb = (XBlock*)c.get(10, ((size_t)T * nb + 1) * sizeof(XBlock));
+      q.nb = T * nb;
+      LLMI_HIP(hipMemcpyAsync(xd, x, xb, hipMemcpyHostToDevice, c.stream));
+      LLMI_HIP(hipMemcpyAsync(od, out, ob, hipMemcpyHostToDevice, c.stream));  // (what the launch does not write stays)
+      launch_quantize_q8_0(xd, T * n_cols, q, c.stream);
+      launch_prefill_gemm(w, q.xb, nb, T, od, ostride, c.stream, kernel == 1 ? 1 : kernel == 2 ? 5 : 0);
+      LLMI_HIP(hipMemcpyAsync(out, od, ob, hipMemcpyDeviceToHost, c.stream));
+      LLMI_HIP(hipStreamSynchronize(c.stream));
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      free_weight(w);
+      throw;
+    }
+    free_weight(w);
+  });
+}
+
 int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits) {
   return guard([&] {
     if (!x16 || !w16 || !logits) throw status_error(LLMI_E_ARG, "logits_rows: null pointer");

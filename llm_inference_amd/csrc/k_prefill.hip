@@ -2047,9 +2047,31 @@ void launch_prefill_gemm16(const DevWeight& w, const uint16_t* x, int xstride, i
   LLMI_HIP(hipGetLastError());
 }
 
+// The kernel launch_prefill_gemm runs for a Q8_0 / Q4_0 weight: 5, or 1 = the skinny int8 kernel (k_gemm_rows.hip),
+// which takes v5's launches at T <= GEMM_ROWS_I8_T_SKINNY (0 as measured: none) and computes v5's bits
+// (LLMI_PG_SKINNY=0: v5 itself, for A/B; a forced v5 geometry, LLMI_PG5=<name>, and v5's development builds stay on
+// v5); 0: none.
+int prefill_gemm_plan(uint32_t type, int rows, int cols, int slab, int T) {
+  DevWeight w;
+  w.type = type;
+  w.rows = rows;
+  w.cols = cols;
+  w.slab = slab;
+  if ((type != T_Q8_0 && type != T_Q4_0) || !prefill_gemm_supported(w)) return 0;
+#if defined(LLMI_PG5_NODMA) || defined(LLMI_PG5_NOCOMP)
+  return 5;
+#endif
+  const char* sk = getenv("LLMI_PG_SKINNY");
+  int t_skinny = GEMM_ROWS_I8_T_SKINNY;  // LLMI_GR_I8_T=<rows>: another switch for A/B (scripts/bench_gemm_rows.py)
+  if (const char* f = getenv("LLMI_GR_I8_T")) t_skinny = std::min(std::max(atoi(f), 0), GEMM_ROWS_I8_T_MAX);
+  return T <= t_skinny && !getenv("LLMI_PG5") && !(sk && atoi(sk) == 0) ? 1 : 5;
+}
+
 void launch_prefill_gemm(const DevWeight& w, const XBlock* x, int xstride, int T, float* out, int ostride,
-                         hipStream_t s) {
+                         hipStream_t s, int force) {
   if (!prefill_gemm_supported(w)) throw std::runtime_error("prefill_gemm: unsupported weight");
+  const int plan = force ? force : prefill_gemm_plan(w.type, w.rows, w.cols, w.slab, T);
+  if (plan == 1 && !gemm_rows_i8_supported(w)) throw std::runtime_error("gemm_rows_i8: unsupported weight");
   PrefillGemm a;
   a.qs = reinterpret_cast<const uint4*>(w.qs);
   a.wd = w.d;
@@ -2065,6 +2087,7 @@ void launch_prefill_gemm(const DevWeight& w, const XBlock* x, int xstride, int T
   a.T = T;
   a.out = out;
   a.ostride = ostride;
+  if (plan == 1) return launch_gemm_rows_i8(a, s);
   if (!launch_gemm5(a, s)) throw std::runtime_error("prefill_gemm: shape outside the v5 geometries");
   LLMI_HIP(hipGetLastError());
 }

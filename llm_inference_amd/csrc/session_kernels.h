@@ -225,8 +225,20 @@ void launch_batch_feedback(const int32_t* argmax, SeqRow* rows, int32_t* tokens,
 constexpr int PREFILL_ATTN_KS_MAX = 8;
 void launch_prefill_norm(const PrefillNorm& a, int T, hipStream_t s);
 bool prefill_gemm_supported(const DevWeight& w);
+// force: 0 the plan below, 1 the skinny int8 kernel, 5 v5 (the op-level entry's choice)
 void launch_prefill_gemm(const DevWeight& w, const XBlock* x, int xstride, int T, float* out, int ostride,
-                         hipStream_t s);
+                         hipStream_t s, int force = 0);
+// The kernel launch_prefill_gemm runs for a Q8_0 / Q4_0 weight [rows][cols] at T token rows: 5, or 1 = the skinny
+// int8 kernel below; 0: the type or shape is outside prefill_gemm_supported.  No GPU work.
+int prefill_gemm_plan(uint32_t type, int rows, int cols, int slab, int T);
+// The skinny int8 GEMM (k_gemm_rows.hip): v5's bits (KQ == 0) for 1 <= T <= GEMM_ROWS_I8_T_MAX
+// rows of Q8_0 activation blocks times a Q8_0 or Q4_0 weight within prefill_gemm_supported
+constexpr int GEMM_ROWS_I8_T_MAX = 32;
+// the rows up to which launch_prefill_gemm picks it: 0, it measured behind v5 on the four projections' sum at 1, 8, 16
+// and 32 rows, so it runs only where asked for -- llmi_gemm_rows_i8(kernel = 1), LLMI_GR_I8_T
+constexpr int GEMM_ROWS_I8_T_SKINNY = 0;
+bool gemm_rows_i8_supported(const DevWeight& w);
+void launch_gemm_rows_i8(const PrefillGemm& a, hipStream_t s);
 // f16 activations (x16 rows scaled per token, tscale = 2^s per token or null for 1): GEMM v7 for Q4_0 weights
 // (the default prefill GEMM where prefill_gemm7_supported), v6 for the K-quants
 bool prefill_gemm16_supported(const DevWeight& w);

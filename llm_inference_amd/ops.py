@@ -279,6 +279,40 @@ def gemm_rows(w_blocks, n_rows: int, n_cols: int, x16, tscale=None, kernel: str 
     return res
 
 
+def gemm_rows_i8_plan(wtype: int, n_rows: int, n_cols: int, T: int) -> int:
+    """llmi_gemm_rows_i8_plan: the kernel gemm_rows_i8(kernel="auto") and the session run for a Q8_0 / Q4_0 weight
+    [n_rows][n_cols] at T token rows -- 1 the skinny int8 kernel, 5 the tiled one, 0
+    unsupported.  No GPU work."""
+    return int(lib().llmi_gemm_rows_i8_plan(int(wtype), int(n_rows), int(n_cols), int(T)))
+
+
+_I8_BLOCK_BYTES = {int(TensorType.Q8_0): 34, int(TensorType.Q4_0): 18}
+
+
+def gemm_rows_i8(w_blocks, wtype: int, n_rows: int, n_cols: int, x, kernel: str = "auto", slab: bool = False,
+                 out=None) -> np.ndarray:
+    """llmi_gemm_rows_i8: the int8 GEMM of the batch steps alone.  w_blocks: Q8_0 (34 B per
+    block) or Q4_0 (18 B) blocks in GGUF form, n_rows x n_cols / 32 of them; x [T][n_cols] float32, quantized on the
+    device to Q8_0 blocks as quantize_row_q8_0 does.  kernel: "auto" (gemm_rows_i8_plan), "skinny" (T <= 32) or
+    "tiled" (v5) -- the last two write the same bits.  slab: repack the Q4_0 weight slab-major as the session does.
+    Returns float32 [T][ostride]: `out` (default zeros [T][n_rows]) with [t][0 .. n_rows) of every row overwritten
+    and nothing else."""
+    wb = np.ascontiguousarray(w_blocks).view(np.uint8).reshape(-1)
+    xf = np.ascontiguousarray(x, np.float32)
+    if kernel not in _GEMM_ROWS_KERNELS:
+        raise ValueError("gemm_rows_i8: kernel must be 'auto', 'skinny' or 'tiled'")
+    bb = _I8_BLOCK_BYTES.get(int(wtype))  # (another type: the library's LLMI_E_TYPE)
+    if xf.ndim != 2 or xf.shape[1] != n_cols or (bb is not None and wb.size != n_rows * (n_cols // 32) * bb):
+        raise ValueError("gemm_rows_i8: x [T][n_cols] and n_rows x n_cols / 32 blocks of wtype")
+    T = xf.shape[0]
+    res = np.zeros((T, n_rows), np.float32) if out is None else np.array(out, np.float32, order="C")
+    if res.ndim != 2 or res.shape[0] != T:
+        raise ValueError("gemm_rows_i8: out must be [T][ostride]")
+    check(lib().llmi_gemm_rows_i8(ptr(wb), int(wtype), int(n_rows), int(n_cols), ptr(xf), T,
+                                  _GEMM_ROWS_KERNELS[kernel], int(bool(slab)), ptr(res), res.shape[1]))
+    return res
+
+
 def logits_rows(x16, w16, softcap: float = 0.0) -> np.ndarray:
     """llmi_logits_rows: the multi-row F16 logits GEMV alone.  x16 [T][E] and w16 [V][E] as
     float16 (or their uint16 bits); returns float32 [T][V] whose row t carries the bits of the fast F16

@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
-"""The skinny GEMM against the tiled launches it replaces, in one process, alternating:
+"""The skinny GEMMs against the tiled launches they replace (DESIGN.md sections 17 and 18), in one process, alternating:
 
   (a) Model.time_kernel(15) -- the four projections' GEMMs of every layer at the row count of a batch step -- as a
       whole and per projection (LLMI_GR_ONLY), default against LLMI_PG_SKINNY=0: median of --repeats with min..max,
       us per layer, and the share of --hbm-gbps the weight bytes reach;
   (b) the batch_generate step at the same B, default against LLMI_PG_SKINNY=0.
+
+--quant q8_0 builds the model with Q8_0 layers and --int8 runs the session with LLMI_PREFILL_F16=0: both put every
+projection on the int8 GEMMs (section 18), and the skinny side then runs with LLMI_GR_I8_T=32 so that every row count
+up to 32 reaches the skinny int8 kernel whatever the committed switch is.
 
 Prints one JSON line."""
 import argparse
@@ -32,12 +36,19 @@ def main():
     p.add_argument("--kernel-reps", type=int, default=5)
     p.add_argument("--batches", default="1,8,32,64")
     p.add_argument("--hbm-gbps", type=float, default=8000.0)
+    p.add_argument("--quant", default="q4_0", choices=("q4_0", "q8_0"))
+    p.add_argument("--int8", action="store_true")
     a = p.parse_args()
+    i8 = a.int8 or a.quant == "q8_0"
+    if a.int8:
+        os.environ["LLMI_PREFILL_F16"] = "0"
+    from llm_inference_amd.gguf import TensorType
     from llm_inference_amd.model import Model
     from llm_inference_amd.synthetic import CONFIGS, build_gemma3_gguf
     cfg = CONFIGS[a.config]
+    wtype = TensorType.Q8_0 if a.quant == "q8_0" else TensorType.Q4_0
     batches = [int(b) for b in a.batches.split(",")]
-    m = Model(build_gemma3_gguf(cfg, seed=1234), max_ctx=a.prefill + a.steps + 8)
+    m = Model(build_gemma3_gguf(cfg, seed=1234, wtype=wtype), max_ctx=a.prefill + a.steps + 8)
     rng = np.random.default_rng(1)
     prompt = np.concatenate([[2], rng.integers(4, cfg.vocab, a.prefill - 1)]).astype(np.int32)
     m.forward(prompt, 0, want_logits=False)
@@ -48,8 +59,11 @@ def main():
 
     def mode(skinny):
         os.environ.pop("LLMI_PG_SKINNY", None)
+        os.environ.pop("LLMI_GR_I8_T", None)
         if not skinny:
             os.environ["LLMI_PG_SKINNY"] = "0"
+        elif i8:
+            os.environ["LLMI_GR_I8_T"] = "32"
 
     def step(B):
         m.sync()
@@ -89,7 +103,8 @@ def main():
                 "skinny_hbm_share": round(by[o] / max(s_["med"], 1e-9) / 1e3 / a.hbm_gbps, 3)}
         rows.append(row)
     mode(True)
-    print(json.dumps({"config": cfg.name, "prefill": a.prefill, "steps": a.steps, "repeats": a.repeats,
+    os.environ.pop("LLMI_GR_I8_T", None)
+    print(json.dumps({"config": cfg.name, "quant": a.quant, "int8": i8, "prefill": a.prefill, "steps": a.steps, "repeats": a.repeats,
                       "hbm_gbps": a.hbm_gbps, "rows": rows}))
     m.close()
 
