@@ -204,6 +204,14 @@ int llmi_session_seq_reserve(llmi_session* s, int n_seq);
 /* K/V rows [0, n_pos) of every layer, slot src -> slot dst (a prompt run by forward() lands in slot 0; this moves
  * or forks it).  Ordered on the session's stream. */
 int llmi_session_seq_copy(llmi_session* s, int dst, int src, int n_pos);
+/* llmi_session_seq_copy -- the same copy, errors (their messages say seq_copy) and ordering -- which also records on
+ * the host that rows [0, n_pos) of dst are src's.  llmi_session_batch_forward and the
+ * llmi_session_batch_generate calls then read the K/V rows that the rows of a step still share once per group of up
+ * to 32 rows, not once per row; the results are the same bits.  A call that writes row p of either slot shortens the
+ * record to p rows.  Groups of fewer than 24 rows run as after llmi_session_seq_copy (they measured slower;
+ * LLMI_BATCH_SHARED_MIN_ROWS at the call sets another minimum, at least 2).  LLMI_BATCH_SHARED=0 in the environment at
+ * a batch call: the records are kept, the step runs as after llmi_session_seq_copy. */
+int llmi_session_seq_share(llmi_session* s, int dst, int src, int n_pos);
 /* One step for B rows: row b runs token tokens[b] at position pos[b] of slot slots[b] (appends its K/V there,
  * attends keys 0..pos[b] of that slot).  argmax[b] / lse[b] (may be NULL) come from the fused scorer; logits
  * ([B][vocab], may be NULL) from the multi-row F16 logits GEMV (one table read per block of rows, section 13; for
@@ -564,6 +572,10 @@ int llmi_session_get_info(const llmi_session* s, llmi_session_info* info);
  *       lookup step made them, at that step's token-row count and on its activation buffers, one pass over the layers
  *       per repetition (the weights come from HBM); us per layer, bytes = one layer's weights (0 / 0 before any such
  *       step, and on tensor-parallel sessions).
+ *  16 = the shared-prefix form of 10 over the same rows, with the most recent batch step's groups
+ *       (llmi_session_seq_share): the groups' pass, the rows' launch from its state and the merge; bytes = K and V rows
+ *       [0, P) once per group plus rows P..pos[b] of every live row, per layer, P the layer's whole rounds of the
+ *       group's shared length (0 / 0 unless that step formed a group).  10 times the unshared form in either case.
  */
 int llmi_session_time_kernel(llmi_session* s, int which, int reps, double* us_per_launch, double* bytes_per_launch);
 

@@ -127,6 +127,7 @@ _SIGS = {
     "llmi_session_score_top": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp]),
     "llmi_session_seq_reserve": (C.c_int, [_vp, C.c_int]),
     "llmi_session_seq_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
+    "llmi_session_seq_share": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "llmi_session_batch_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "llmi_session_batch_extend": (C.c_int, [_vp, _vp, C.POINTER(Span), C.c_int, _vp, _vp, _vp]),
     "llmi_session_batch_generate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),

@@ -466,6 +466,13 @@ int llmi_session_seq_copy(llmi_session* s, int dst, int src, int n_pos) {
   });
 }
 
+int llmi_session_seq_share(llmi_session* s, int dst, int src, int n_pos) {
+  return guard([&] {
+    if (!s) throw status_error(LLMI_E_ARG, "seq_copy: null pointer");
+    s->s->seq_share(dst, src, n_pos);
+  });
+}
+
 int llmi_session_batch_forward(llmi_session* s, const int32_t* tokens, const int32_t* slots, const int32_t* pos,
                                int B, float* logits, int32_t* argmax, float* lse) {
   return guard([&] {

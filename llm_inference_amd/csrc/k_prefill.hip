@@ -17,6 +17,7 @@
 // against the token loop and the reference (tests/test_prefill.py).
 #include "attn.h"
 #include "session_kernels.h"
+#include <type_traits>
 
 namespace llmi {
 
@@ -1505,8 +1506,13 @@ __device__ __forceinline__ void attn_emit(const PrefillAttn& a, const v16f (&o)[
 // the single-sequence launch's query block of blocks[i].n tokens at pos0 = blocks[i].pos on its slot's caches,
 // instruction for instruction (columns past n repeat the last query, as a prompt's last block does; they write no
 // partial and no output)
-template <int HD, int G, int S, bool MS = false, bool SP = false>
-__global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAttn a, int T) {
+// SH (with MS): the second launch of the shared-prefix form (AttnShare) -- row b's
+// rounds below share_len[b] / (32 S) were run by prefill_attn_shared_kernel: a work-group that owns some of them
+// takes every wave's (m, l, O^T) from sstate and goes on at its first own round at or past that; a row with
+// share_len 0 runs as without SH
+template <int HD, int G, int S, bool MS = false, bool SP = false, bool SH = false>
+__global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(
+    std::conditional_t<SH, PrefillAttnShared, PrefillAttn> a, int T) {
   constexpr int U = HD / 8;                // 16-B units per cache row
   constexpr int SWM = U < 16 ? U - 1 : 15;  // swizzle mask (units)
   constexpr int ROWB = HD * 2;              // bytes per cache row
@@ -1570,7 +1576,12 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
       glds16(src, tile_ptr(lr, j) + kind * TILE + pp * 1024);
     }
   };
-  issue(0);
+  int lr0 = 0;  // SH: this work-group's local rounds below the row's shared length (run by the first launch)
+  if constexpr (SH) {
+    const int pre = a.sh.share_len[qb] / (32 * S);
+    lr0 = ks < pre ? (pre - ks + KS - 1) / KS : 0;
+  }
+  if (!SH || lr0 < my_rounds) issue(lr0);
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   // Q^T fragments: lane (query r, h) holds q[d = 16 c + 8 h .. + 7]
   f16x8 qf[HD / 16];
@@ -1581,8 +1592,22 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
 #pragma unroll
   for (int i = 0; i < HD / 32; i++) o[i] = v16f{};
   float m_run = -INFINITY, l_run = 0.0f;
+  if constexpr (SH) {
+    if (lr0 > 0) {  // the row's column of the first launch, into all 32 columns (as they all hold the one query)
+      const float* st = a.sh.sstate + ((((size_t)qb * a.n_head + hq) * KS + ks) * S + sp) * SHARE_STATE(HD);
+#pragma unroll
+      for (int i = 0; i < HD / 32; i++)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; q4++) {
+          const float4 v = reinterpret_cast<const float4*>(st)[(i * 4 + q4) * 2 + h];
+          o[i][4 * q4] = v.x, o[i][4 * q4 + 1] = v.y, o[i][4 * q4 + 2] = v.z, o[i][4 * q4 + 3] = v.w;
+        }
+      m_run = st[HD];
+      l_run = st[HD + 1];
+    }
+  }
   const int lg = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;  // tr_b16 group / position
-  for (int lr = 0; lr < my_rounds; lr++) {
+  for (int lr = lr0; lr < my_rounds; lr++) {
     vm_wait<0>();
     __builtin_amdgcn_s_barrier();  // round landed in every wave; the previous round's half is free
     if (lr + 1 < my_rounds) issue(lr + 1);
@@ -1697,6 +1722,132 @@ __global__ __launch_bounds__(64 * G * S) void prefill_attn_mfma_kernel(PrefillAt
   // O = O^T / l -> Q8_0 blocks (32 head dims = one tile column; lanes q and q + 32 hold 16 each), or f16
   if (tok0 + r >= T) return;  // after the last LDS read: the partner lane of a live query is also out
   attn_emit<HD, HD / 32>(a, o, l_run, 0, otok0 + r, hq, h);
+}
+
+// The shared-prefix pass of a multi-sequence step (AttnShare).  Grid (kv head, group,
+// key split), G S waves as prefill_attn_mfma_kernel<HD, G, S>.  Query column r is the group's member r (columns past
+// the member count repeat the last member and write nothing), so one K / V tile of the leader's caches serves up to 32
+// rows of the step.  Work-group ks runs the rounds q = ks (mod KS) below len / (32 S), wave sp the tile S q + sp of
+// each: the tiles, in the order, that the unshared launch gives work-group ks / wave sp of every member row -- same
+// ring, pieces and swizzle, same MFMA operand order, soft-cap, expf chain and o *= alpha.  Every key is below every
+// member's position, so there is no mask.  No merge and no output: each wave leaves its columns' (O^T, m, l) in
+// sstate, where the second launch (prefill_attn_mfma_kernel<.., SH>) picks its row's up.
+template <int HD, int G, int S>
+__global__ __launch_bounds__(64 * G * S) void prefill_attn_shared_kernel(PrefillAttnShared a) {
+  constexpr int U = HD / 8;                // 16-B units per cache row
+  constexpr int SWM = U < 16 ? U - 1 : 15;  // swizzle mask (units)
+  constexpr int ROWB = HD * 2;              // bytes per cache row
+  constexpr int TILE = 32 * ROWB;           // bytes per K (or V) tile
+  constexpr int NW = G * S;                 // waves: head g = w % G, key split s = w / G
+  constexpr int P = S * 2 * TILE / 1024;    // DMA pieces per round (S tiles, K then V)
+  static_assert(P % NW == 0 && P / NW <= 63, "pieces");
+  constexpr int RPP = 1024 / ROWB;          // cache rows per piece
+  constexpr int RING = 2 * S * 2 * TILE;    // two rounds of S tiles
+  __shared__ __attribute__((aligned(16))) unsigned char s_kv[RING];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, h = lane >> 5;
+  const int g = w % G, sp = w / G;
+  const int hk = blockIdx.x, hq = hk * G + g;
+  const ShareGroup* gr = a.sh.groups + blockIdx.y;
+  const int n_mem = min(max(gr->n, 1), 32), pre =min(gr->len, a.max_ctx) / (32 * S);  // whole rounds: all of them full
+  const int KS = a.ks, ks = blockIdx.z;
+  if (ks >= pre) return;  // whole work-group, before any barrier
+  const int member = gr->rows[min(r, n_mem - 1)];
+  const bool live = r < n_mem && a.rows[member].pos >= 0;  // (an ended row of the loop: a column that writes nothing)
+  if (__builtin_amdgcn_ballot_w64(live) == 0) return;     // every wave holds the same columns: whole work-group
+  const int my_rounds = (pre - ks + KS - 1) / KS;
+  const uint16_t *kc = a.kv_tab[2 * gr->slot], *vc = a.kv_tab[2 * gr->slot + 1];
+  const size_t cache0 = (size_t)hk * a.max_ctx;
+  auto tile_ptr = [&](int lr, int j) { return s_kv + ((lr & 1) * S + j) * 2 * TILE; };
+  auto issue = [&](int lr) {
+    const int round = ks + lr * KS;
+#pragma unroll
+    for (int i = 0; i < P / NW; i++) {
+      const int p = w + i * NW, j = p / (2 * TILE / 1024), q = p % (2 * TILE / 1024);
+      const int kind = q / (TILE / 1024), pp = q % (TILE / 1024);
+      const int row = pp * RPP + lane / U, slot = lane % U, u = slot ^ (row & SWM);
+      const int key = min(32 * (S * round + j) + row, a.max_ctx - 1);
+      const uint16_t* src = (kind ? vc : kc) + (cache0 + key) * HD + u * 8;
+      glds16(src, tile_ptr(lr, j) + kind * TILE + pp * 1024);
+    }
+  };
+  issue(0);
+  typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+  // Q^T fragments: lane (column r, h) holds member r's q[d = 16 c + 8 h .. + 7]
+  f16x8 qf[HD / 16];
+  const uint4* qrow = reinterpret_cast<const uint4*>(a.q + ((size_t)member * a.n_head + hq) * HD);
+#pragma unroll
+  for (int c = 0; c < HD / 16; c++) qf[c] = __builtin_bit_cast(f16x8, qrow[2 * c + h]);
+  v16f o[HD / 32];
+#pragma unroll
+  for (int i = 0; i < HD / 32; i++) o[i] = v16f{};
+  float m_run = -INFINITY, l_run = 0.0f;
+  const int lg = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;  // tr_b16 group / position
+  for (int lr = 0; lr < my_rounds; lr++) {
+    vm_wait<0>();
+    __builtin_amdgcn_s_barrier();  // round landed in every wave; the previous round's half is free
+    if (lr + 1 < my_rounds) issue(lr + 1);
+    const unsigned char* kt = tile_ptr(lr, sp);
+    const unsigned char* vt = kt + TILE;
+    v16f sc = {};
+#pragma unroll
+    for (int c = 0; c < HD / 16; c++) {
+      const f16x8 kf = *reinterpret_cast<const f16x8*>(kt + r * ROWB + (((2 * c + h) ^ (r & SWM)) * 16));
+      sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc, 0, 0, 0);
+    }
+    if (a.softcap > 0.0f) {
+#pragma unroll
+      for (int reg = 0; reg < 16; reg++) sc[reg] = a.softcap * tanhf(sc[reg] / a.softcap);
+    }
+    float mt = -INFINITY;
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) mt = fmaxf(mt, sc[reg]);
+    mt = fmaxf(mt, __shfl_xor(mt, 32));
+    const float m_new = fmaxf(m_run, mt);
+    const float alpha = m_new == -INFINITY ? 1.0f : expf(m_run - m_new);
+    float ps = 0.0f;
+    f16x8 pb[2];
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+      const float pv = m_new == -INFINITY ? 0.0f : expf(sc[reg] - m_new);
+      ps += pv;
+      pb[reg >> 3][reg & 7] = (_Float16)pv;
+    }
+    ps += __shfl_xor(ps, 32);
+    l_run = l_run * alpha + ps;
+    m_run = m_new;
+#pragma unroll
+    for (int i = 0; i < HD / 32; i++) o[i] *= alpha;
+#pragma unroll
+    for (int kk = 0; kk < 2; kk++) {
+#pragma unroll
+      for (int i = 0; i < HD / 32; i++) {
+        const int gh = lg >> 1;
+        const int col = 32 * i + 16 * (lg & 1) + 4 * tp;
+        f16x4 vv[2];  // (the v4f16 form, as prefill_attn_mfma_kernel)
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+          const int key = 16 * kk + 4 * gh + 8 * e + tq;
+          const int off = key * ROWB + (((col >> 3) ^ (key & SWM)) * 16) + (col & 7) * 2;
+          vv[e] = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                                                 (__attribute__((address_space(3))) fp16x4*)(vt + off)));
+        }
+        const f16x8 vf = __builtin_shufflevector(vv[0], vv[1], 0, 1, 2, 3, 4, 5, 6, 7);
+        o[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pb[kk], o[i], 0, 0, 0);
+      }
+    }
+  }
+  if (!live) return;
+  float* st = a.sh.sstate + ((((size_t)member * a.n_head + hq) * KS + ks) * S + sp) * SHARE_STATE(HD);
+#pragma unroll
+  for (int i = 0; i < HD / 32; i++)
+#pragma unroll
+    for (int q4 = 0; q4 < 4; q4++)
+      reinterpret_cast<float4*>(st)[(i * 4 + q4) * 2 + h] =
+          make_float4(o[i][4 * q4], o[i][4 * q4 + 1], o[i][4 * q4 + 2], o[i][4 * q4 + 3]);
+  if (h == 0) {
+    st[HD] = m_run;
+    st[HD + 1] = l_run;
+  }
 }
 
 // Key-split partials of the query blocks that have more than one (prefill_attn_mfma_kernel, a.ks > 1): one wave
@@ -2121,13 +2272,36 @@ void launch_prefill_qk(const PrefillQK& a, int T, hipStream_t s) {
 // (correct, slower).  Returns S, 0 for a group it does not cover.
 template <int HD, bool MS, bool SP = false>
 static int launch_attn_mfma(const PrefillAttn& a, int T, const dim3& grid, hipStream_t s) {
-  constexpr int S4 = HD >= 256 ? 2 : 4;
-  constexpr int SG4 = HD == 128 ? 2 : S4;
+  constexpr int S4 = prefill_attn_splits(HD, 1);
+  constexpr int SG4 = prefill_attn_splits(HD, 4);
+  static_assert(prefill_attn_splits(HD, 2) == S4, "splits");
   switch (a.n_head / a.n_head_kv) {
     case 1: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 1, S4, MS, SP>), grid, dim3(64 * S4), 0, s, a, T); return S4;
     case 2: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 2, S4, MS, SP>), grid, dim3(128 * S4), 0, s, a, T); return S4;
     case 4: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 4, SG4, MS, SP>), grid, dim3(256 * SG4), 0, s, a, T); return SG4;
     default: return 0;
+  }
+}
+// The shared-prefix form's launches from the same table: PRE its first (prefill_attn_shared_kernel over the groups),
+// otherwise its second (the multi-sequence kernel from the first one's state).
+template <int HD, bool PRE>
+static int launch_attn_shared(const PrefillAttnShared& a, int T, const dim3& grid, hipStream_t s) {
+  constexpr int S4 = prefill_attn_splits(HD, 1);
+  constexpr int SG4 = prefill_attn_splits(HD, 4);
+  if constexpr (PRE) {
+    switch (a.n_head / a.n_head_kv) {
+      case 1: hipLaunchKernelGGL((prefill_attn_shared_kernel<HD, 1, S4>), grid, dim3(64 * S4), 0, s, a); return S4;
+      case 2: hipLaunchKernelGGL((prefill_attn_shared_kernel<HD, 2, S4>), grid, dim3(128 * S4), 0, s, a); return S4;
+      case 4: hipLaunchKernelGGL((prefill_attn_shared_kernel<HD, 4, SG4>), grid, dim3(256 * SG4), 0, s, a); return SG4;
+      default: return 0;
+    }
+  } else {
+    switch (a.n_head / a.n_head_kv) {
+      case 1: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 1, S4, true, false, true>), grid, dim3(64 * S4), 0, s, a, T); return S4;
+      case 2: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 2, S4, true, false, true>), grid, dim3(128 * S4), 0, s, a, T); return S4;
+      case 4: hipLaunchKernelGGL((prefill_attn_mfma_kernel<HD, 4, SG4, true, false, true>), grid, dim3(256 * SG4), 0, s, a, T); return SG4;
+      default: return 0;
+    }
   }
 }
 
@@ -2136,15 +2310,28 @@ static int launch_attn_mfma(const PrefillAttn& a, int T, const dim3& grid, hipSt
 // before any barrier (as a short query block does there).  The merge runs when a.pos0 -- here the LONGEST row's
 // position, a host-side bound -- has more than one partial; each row's merge work-groups decide for themselves.
 // head_dim 128 / 256 (the sizes the tests cover), Q8_0 or f16 outputs.
+// sh: the shared-prefix form -- the groups' pass, then the rows from its state; the merge as it is.
 template <int HD>
-static void attn_rows(const PrefillAttn& a, int T, hipStream_t s) {
+static void attn_rows(const PrefillAttn& a, int T, hipStream_t s, const AttnShare* sh = nullptr) {
   if constexpr (HD < 128) {
     throw std::runtime_error("prefill_attn: the multi-sequence form needs head_dim 128 or 256");
   } else {
     if (!a.kv_tab || getenv("LLMI_PREFILL_ATTN_V1") || a.q8k || !a.part || a.ks < 1 || a.ks > PREFILL_ATTN_KS_MAX)
       throw std::runtime_error("prefill_attn: the multi-sequence form needs the MFMA kernel, Q8_0 / f16 outputs and "
                                "the partial scratch");
-    const int S = launch_attn_mfma<HD, true>(a, T, dim3(a.n_head_kv, T, a.ks), s);
+    int S;
+    if (sh) {
+      if (!sh->groups || sh->n_groups < 1 || !sh->share_len || !sh->sstate)
+        throw std::runtime_error("prefill_attn: the shared-prefix form needs the group table, the rows' shared lengths "
+                                 "and the state scratch");
+      PrefillAttnShared as;
+      static_cast<PrefillAttn&>(as) = a;
+      as.sh = *sh;
+      launch_attn_shared<HD, true>(as, T, dim3(a.n_head_kv, sh->n_groups, a.ks), s);
+      S = launch_attn_shared<HD, false>(as, T, dim3(a.n_head_kv, T, a.ks), s);
+    } else {
+      S = launch_attn_mfma<HD, true>(a, T, dim3(a.n_head_kv, T, a.ks), s);
+    }
     if (!S) throw std::runtime_error("prefill_attn: the multi-sequence form needs GQA group 1, 2 or 4");
     if (a.ks > 1 && a.pos0 / 32 + 1 > S)
       hipLaunchKernelGGL((prefill_attn_merge_kernel<HD, 1, true>), dim3(a.n_head, T, HD / 32), dim3(64), 0, s, a, T, S);
@@ -2204,6 +2391,16 @@ static void attn_g(const PrefillAttn& a, int T, hipStream_t s) {
     case 4: hipLaunchKernelGGL((prefill_attn_kernel<HD, 4>), grid, dim3(256), 0, s, a); break;
     default: throw std::runtime_error("prefill_attn: GQA group must be 1, 2 or 4");
   }
+}
+
+void launch_prefill_attn_shared(const PrefillAttn& a, const AttnShare& sh, int T, hipStream_t s) {
+  if (!a.rows || a.blocks) throw std::runtime_error("prefill_attn: the shared-prefix form is the multi-sequence form's");
+  switch (a.head_dim) {
+    case 128: attn_rows<128>(a, T, s, &sh); break;
+    case 256: attn_rows<256>(a, T, s, &sh); break;
+    default: throw std::runtime_error("prefill_attn: the multi-sequence form needs head_dim 128 or 256");
+  }
+  LLMI_HIP(hipGetLastError());
 }
 
 void launch_prefill_attn(const PrefillAttn& a, int T, hipStream_t s) {

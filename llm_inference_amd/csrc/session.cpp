@@ -1151,7 +1151,9 @@ void Session::prefill_layers(const int32_t* d_tokens, int T, int p0, bool trim, 
     at.kv_tab = qk.kv_tab;
     at.blocks = blocks;
     at.n_blocks = n_blocks;
-    if (rows) launch_batch_attn(at, Tq, s);
+    if (rows && !blocks && sh_step_groups_ > 0)  // a batch step with forked rows: the shared-prefix form (section 19)
+      launch_prefill_attn_shared(at, AttnShare{bt_groups_, sh_step_groups_, bt_share_len_, bt_sstate_}, Tq, s);
+    else if (rows) launch_batch_attn(at, Tq, s);
     else launch_prefill_attn(at, Tq, s);
     if (rows) {  // time_kernel(10), or (a batch_extend step) time_kernel(12)
       std::vector<PrefillAttn>& last = bx_step_ ? bx_last_attn_ : bt_last_attn_;
@@ -1910,6 +1912,7 @@ void Session::forward(const int32_t* tokens, int n, int pos, float* logits, int3
   if (pos < 0 || pos + n > max_ctx_) throw status_error(LLMI_E_RANGE, "forward: context overflow");
   for (int i = 0; i < n; i++)
     if (tokens[i] < 0 || tokens[i] >= vocab_) throw status_error(LLMI_E_RANGE, "forward: token id out of range");
+  share_write(0, pos);  // (slot 0's rows from pos on change: section 19's links)
   tp_guarded([&] {
     if (n > 1 && prefill_ok_ && getenv("LLMI_NO_PREFILL") == nullptr) {
       set_token_pos(tokens[n - 1], pos + n - 1, true);  // what the token loop leaves behind
@@ -2085,6 +2088,7 @@ void Session::score(const int32_t* tokens, int n, int pos, const int32_t* target
     sc_h_tgt_[(size_t)i] = t;
   }
   ensure_usable();
+  share_write(0, pos);
   sc_top_n_ = top_n;
   ScopeExit top_off{[&] { sc_top_n_ = 0; }};
   sc_h_top_id_.assign((size_t)n * top_n, 0);
@@ -2141,6 +2145,7 @@ void Session::forward_trace(const int32_t* tokens, int n, int pos, bool gen, llm
   for (int i = 0; i < n; i++)
     if (tokens[i] < 0 || tokens[i] >= vocab_) throw status_error(LLMI_E_RANGE, "trace: token id out of range");
   if (score && tp_) throw status_error(LLMI_E_ARG, "trace: scoring runs on one device only (tensor-parallel session)");
+  share_write(0, pos);
   if (score) {  // the targets of llmi_session_score(targets = NULL): the next tokens
     sc_h_tgt_.assign((size_t)n, -1);
     for (int i = 0; i + 1 < n; i++) sc_h_tgt_[(size_t)i] = tokens[i + 1];
@@ -2182,6 +2187,7 @@ void Session::forward_dump(const int32_t* tokens, int n, int pos, const char* pa
   for (int i = 0; i < n; i++)
     if (tokens[i] < 0 || tokens[i] >= vocab_) throw status_error(LLMI_E_RANGE, "dump: token id out of range");
   if (tp_) throw status_error(LLMI_E_ARG, "dump: one device only");
+  share_write(0, pos);
   std::FILE* f = std::fopen(path, "a");
   if (!f) throw status_error(LLMI_E_ARG, std::string("dump: cannot open ") + path);
   const bool graph = use_graph_;
@@ -2209,6 +2215,7 @@ void Session::forward_dump(const int32_t* tokens, int n, int pos, const char* pa
 void Session::enqueue(int32_t first, int pos, int n_steps) {
   if (first < 0 || first >= vocab_) throw status_error(LLMI_E_RANGE, "token id out of range");
   if (pos < 0 || pos + n_steps > max_ctx_) throw status_error(LLMI_E_RANGE, "generate: context overflow");
+  share_write(0, pos);
   tp_guarded([&] {
     set_token_pos(first, pos, true);
     // the folded step graph starts at layer 0: the first embedding here
@@ -2430,6 +2437,7 @@ void Session::time_kernel(int which, int reps, double* us, double* bytes) {
   if (which == 13) return time_lookup_step(reps, us, bytes);
   if (which == 14) return time_lookup_select(reps, us, bytes);
   if (which == 15) return time_gemm_rows(reps, us, bytes);
+  if (which == 16) return time_shared_attn(reps, us, bytes);
   if (which == 9) {  // the fused scorer's two launches over the most recently scored chunk (its rows are still there)
     *us = *bytes = 0.0;
     if (score_path() != 1 || sc_last_T_ <= 0 || reps <= 0) return;

@@ -106,6 +106,8 @@ class Session {
   void seq_reserve(int n_seq);
   int n_seq() const { return n_seq_; }
   void seq_copy(int dst, int src, int n_pos);
+  // seq_copy, and the link: rows [0, n_pos) of dst are src's, so batch steps read them once
+  void seq_share(int dst, int src, int n_pos);
   void batch_forward(const int32_t* tokens, const int32_t* slots, const int32_t* pos, int B, float* logits,
                      int32_t* argmax, float* lse);
   void batch_generate(const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
@@ -398,6 +400,29 @@ class Session {
   void step_tail(uint16_t* x16, const OutRun* runs, size_t n_runs, const std::vector<OutRow0>& r0, bool score);
   void ensure_batch_apart();  // bt_apart_
   void time_batch_attn(int reps, double* us, double* bytes);
+  // shared prefixes (llmi_session_seq_share), host bookkeeping: slot q's K/V rows [0, sh_n_[q])
+  // are bit-equal to those of slot sh_leader_[q], the root of its chain (a slot with no link: itself, 0 rows).  A
+  // leader is never a follower, and a link of 0 rows is dropped.
+  int sh_leader_[LLMI_SEQ_MAX], sh_n_[LLMI_SEQ_MAX];
+  // K/V row p of `slot` is about to be written (the host-known start of a call: device loops only move forward)
+  void share_write(int slot, int p) {
+    if (!seq_reserved_) return;
+    for (int q = 0; q < LLMI_SEQ_MAX; q++)
+      if (sh_leader_[q] != q && (q == slot || sh_leader_[q] == slot) && p < sh_n_[q]) {
+        sh_n_[q] = p;
+        if (p == 0) sh_leader_[q] = q;
+      }
+  }
+  // the live rows of a batch call grouped by leader into bt_groups_ / bt_share_len_ (device), for every step of the
+  // call; returns the group count (0: LLMI_BATCH_SHARED=0, or no group of 2 rows with a whole round to share)
+  int share_groups(const int32_t* slots, const int32_t* pos, int B);
+  int sh_step_groups_ = 0;               // groups of the step prefill_layers is enqueuing (0: the unshared launches)
+  ShareGroup* bt_groups_ = nullptr;      // [LLMI_SEQ_MAX / 2]
+  int32_t* bt_share_len_ = nullptr;      // [LLMI_SEQ_MAX] per row
+  float* bt_sstate_ = nullptr;           // PrefillAttn::sstate
+  std::vector<ShareGroup> sh_last_groups_;   // the most recent batch step's table (time_kernel(16)); empty: no group
+  std::vector<int32_t> sh_last_len_;
+  void time_shared_attn(int reps, double* us, double* bytes);
   // the batch loop: greedy (samplers null: batch_generate) or with a sampler per row
   void batch_loop(const char* fn, const int32_t* first, const int32_t* slots, const int32_t* pos, int B, int n_steps,
                   const int32_t* stop, int n_stop, const llmi_sampler* samplers, int32_t* out);

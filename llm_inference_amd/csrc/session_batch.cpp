@@ -53,6 +53,7 @@ void Session::seq_reserve(int n_seq) {
     bt_row0_ = dalloc<uint16_t>((size_t)LLMI_SEQ_MAX * hp_.n_embd);
     bt_r0_lse_ = dalloc<float>(2 * LLMI_SEQ_MAX);
     bt_r0_amax_ = dalloc<int32_t>(LLMI_SEQ_MAX);
+    for (int q = 0; q < LLMI_SEQ_MAX; q++) sh_leader_[q] = q, sh_n_[q] = 0;
   }
   // the slots below n_seq that have no cache yet: their own allocations (zeroed on the stream), so a larger reserve
   // moves nothing, and a call that failed partway leaves entries the next call keeps
@@ -74,6 +75,7 @@ void Session::seq_copy(int dst, int src, int n_pos) {
   if (n_pos < 0 || n_pos > max_ctx_) throw status_error(LLMI_E_RANGE, "seq_copy: rows past max_ctx (n_pos)");
   ensure_usable();
   if (dst == src || n_pos == 0) return;
+  share_write(dst, 0);  // dst's rows change: its own link and its followers' go
   for (int l = 0; l < hp_.n_layer; l++) {
     const size_t pitch = (size_t)max_ctx_ * L_[(size_t)l].hd * 2, width = (size_t)n_pos * L_[(size_t)l].hd * 2;
     for (int kv = 0; kv < 2; kv++)  // one strided copy per layer and cache: n_head_kv runs of n_pos rows
@@ -81,6 +83,62 @@ void Session::seq_copy(int dst, int src, int n_pos) {
                                 bt_h_kvtab_[((size_t)l * LLMI_SEQ_MAX + src) * 2 + kv], pitch, width, (size_t)nkv_,
                                 hipMemcpyDeviceToDevice, stream_));
   }
+}
+
+void Session::seq_share(int dst, int src, int n_pos) {
+  seq_copy(dst, src, n_pos);
+  if (dst == src || n_pos == 0) return;
+  // to the root of src's chain, as far as src's rows are the root's (seq_copy has dropped the links dst had, a link
+  // of src to dst among them, so the root is no follower)
+  const bool linked = sh_leader_[src] != src;
+  sh_n_[dst] = linked ? std::min(n_pos, sh_n_[src]) : n_pos;
+  sh_leader_[dst] = sh_leader_[src];
+}
+
+// Rows whose slots hang on one leader (the leader's own row among them), at most 32 to a group in row order; a row
+// takes part with min(its link's rows, its position) -- its position, for the leader -- and only if that is a whole
+// round of some layer; the group shares the smallest of them, floored per layer to that layer's rounds by the kernels.
+int Session::share_groups(const int32_t* slots, const int32_t* pos, int B) {
+  sh_last_groups_.clear();
+  sh_last_len_.assign((size_t)B, 0);
+  const char* off = getenv("LLMI_BATCH_SHARED");
+  if (off && atoi(off) == 0) return 0;
+  // the smallest group worth its extra launch (DESIGN.md section 19.5's measurements); LLMI_BATCH_SHARED_MIN_ROWS,
+  // read at the call, sets another (2: every group the kernels can run -- the tests' small shapes)
+  int min_rows = SHARE_MIN_ROWS;
+  if (const char* c = getenv("LLMI_BATCH_SHARED_MIN_ROWS")) min_rows = std::max(2, atoi(c));
+  int round = max_ctx_ + 1, state = 0;  // the shortest round of any layer (keys); the largest state per (row, head, ks)
+  for (const auto& l : L_) {
+    const int S = prefill_attn_splits(l.hd, nh_ / std::max(nkv_, 1));
+    round = std::min(round, 32 * S);
+    state = std::max(state, S * SHARE_STATE(l.hd));
+  }
+  auto len_of = [&](int b) { return sh_leader_[slots[b]] == slots[b] ? pos[b] : std::min(sh_n_[slots[b]], pos[b]); };
+  bool done[LLMI_SEQ_MAX] = {};
+  for (int b = 0; b < B; b++) {
+    if (done[b] || len_of(b) < round) continue;
+    ShareGroup g{};
+    g.slot = sh_leader_[slots[b]];
+    g.len = max_ctx_;
+    for (int c = b; c < B && g.n < 32; c++) {
+      if (done[c] || sh_leader_[slots[c]] != g.slot || len_of(c) < round) continue;
+      done[c] = true;
+      g.rows[g.n++] = c;
+      g.len = std::min(g.len, len_of(c));
+    }
+    if (g.n < min_rows) continue;
+    for (int i = 0; i < g.n; i++) sh_last_len_[(size_t)g.rows[i]] = g.len;
+    sh_last_groups_.push_back(g);
+  }
+  if (sh_last_groups_.empty()) return 0;
+  if (!bt_groups_) {
+    bt_groups_ = dalloc<ShareGroup>(LLMI_SEQ_MAX / 2);
+    bt_share_len_ = dalloc<int32_t>(LLMI_SEQ_MAX);
+    bt_sstate_ = dalloc<float>((size_t)LLMI_SEQ_MAX * nh_ * PREFILL_ATTN_KS_MAX * state);
+  }
+  h2d(bt_groups_, sh_last_groups_.data(), sh_last_groups_.size() * sizeof(ShareGroup));
+  h2d(bt_share_len_, sh_last_len_.data(), (size_t)B * 4);
+  return (int)sh_last_groups_.size();
 }
 
 void Session::batch_check(const char* fn, const int32_t* tokens, const int32_t* slots, const int32_t* pos, int B,
@@ -247,7 +305,12 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
   };
   std::vector<int> all((size_t)B);
   for (int b = 0; b < B; b++) all[(size_t)b] = b;
-  if (!run(all, true)) return;
+  for (int b = 0; b < B; b++) share_write(slots[b], pos[b]);
+  {
+    sh_step_groups_ = share_groups(slots, pos, B);
+    ScopeExit off{[&] { sh_step_groups_ = 0; }};
+    if (!run(all, true)) return;
+  }
   // the f16 path (Session::prefill's rule, per row): a row whose final norm came out non-finite runs again on the
   // int8 path, which rewrites the same K / V row
   std::vector<int> bad;
@@ -257,8 +320,9 @@ void Session::batch_forward(const int32_t* tokens, const int32_t* slots, const i
         bad.push_back(b);
         break;
       }
-  if (!bad.empty()) {
+  if (!bad.empty()) {  // (unshared: the rows of this smaller step are not the group table's)
     pf_f16_redo_++;
+    sh_last_groups_.clear();
     run(bad, false);
   }
 }
@@ -322,6 +386,7 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
   for (int t = 0; t < total; t++)
     if (tokens[t] < 0 || tokens[t] >= vocab_) throw status_error(LLMI_E_RANGE, f + "token id out of range (tokens)");
   ensure_usable();
+  for (int i = 0; i < n_spans; i++) share_write(spans[i].slot, spans[i].pos);
   hipStream_t s = stream_;
   const int E = hp_.n_embd;
   ensure_extend_buffers();
@@ -507,6 +572,11 @@ void Session::batch_loop(const char* fn, const int32_t* first, const int32_t* sl
   }
   h2d(bt_rows_, rows.data(), (size_t)B * sizeof(SeqRow));
   h2d(bt_tok_, first, (size_t)B * 4);
+  // the group table once, for every step: rows only move forward, and a row that stops becomes a column that writes
+  // nothing
+  for (int b = 0; b < B; b++) share_write(slots[b], pos[b]);
+  sh_step_groups_ = share_groups(slots, pos, B);
+  ScopeExit sh_off{[&] { sh_step_groups_ = 0; }};
   // every step's launches are enqueued at once: tokens, positions, the ids and the stop flags stay on the device
   // (max_pos + i bounds the longest live row: it only decides whether the attention's merge is launched)
   for (int i = 0; i < n_steps; i++) {
@@ -652,6 +722,7 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
   const char* ng_env = getenv("LLMI_LOOKUP_NO_GATHER");
   const bool gather = !(ng_env && atoi(ng_env) == 1) && logits_rows_rb(hp_.n_embd) != 0;
   ensure_usable();
+  for (int b = 0; b < B; b++) share_write(slots[b], pos[b]);
   int group = 4;
   if (const char* c = getenv("LLMI_LOOKUP_SYNC")) group = std::max(1, atoi(c));
   const int cap_steps = max_steps == 0 ? max_new : max_steps;
@@ -859,7 +930,40 @@ void Session::time_batch_attn(int reps, double* us, double* bytes) {
       PrefillAttn at = bt_last_attn_[(size_t)l];
       at.rows = bt_trows_;
       at.pos0 = max_pos;
-      launch_prefill_attn(at, B, s);
+      launch_prefill_attn(at, B, s);  // (the unshared form, whichever the step ran)
+    }
+  }) * 1000.0 / reps / NL;
+  *bytes = by / NL;
+}
+
+// time_kernel(16): the shared-prefix form over the same rows -- the groups' pass, the rows from its state, the merge --
+// with the most recent batch step's group table; bytes: K and V rows [0, P) once per group plus rows P_b .. pos[b] of
+// every live row, P the layer's floor of the shared length.  0 / 0 when that step formed no group.
+void Session::time_shared_attn(int reps, double* us, double* bytes) {
+  *us = *bytes = 0.0;
+  const int NL = hp_.n_layer, B = (int)bt_last_rows_.size();
+  if (sh_last_groups_.empty() || (int)sh_last_len_.size() != B || (int)bt_last_attn_.size() != NL || reps <= 0) return;
+  hipStream_t s = stream_;
+  h2d(bt_trows_, bt_last_rows_.data(), (size_t)B * sizeof(SeqRow));
+  h2d(bt_groups_, sh_last_groups_.data(), sh_last_groups_.size() * sizeof(ShareGroup));
+  h2d(bt_share_len_, sh_last_len_.data(), (size_t)B * 4);
+  int max_pos = 0;
+  double by = 0.0;
+  for (const auto& r : bt_last_rows_) max_pos = std::max(max_pos, r.pos);
+  for (int l = 0; l < NL; l++) {
+    const int round = 32 * prefill_attn_splits(L_[(size_t)l].hd, nh_ / std::max(nkv_, 1));
+    const double row = 2.0 * nkv_ * L_[(size_t)l].hd * 2.0;
+    for (const auto& g : sh_last_groups_) by += (double)(g.len / round * round) * row;
+    for (int b = 0; b < B; b++)
+      if (bt_last_rows_[(size_t)b].pos >= 0)
+        by += (double)(bt_last_rows_[(size_t)b].pos + 1 - sh_last_len_[(size_t)b] / round * round) * row;
+  }
+  *us = time_reps(s, reps, [&] {
+    for (int l = 0; l < NL; l++) {
+      PrefillAttn at = bt_last_attn_[(size_t)l];
+      at.rows = bt_trows_;
+      at.pos0 = max_pos;
+      launch_prefill_attn_shared(at, AttnShare{bt_groups_, (int)sh_last_groups_.size(), bt_share_len_, bt_sstate_}, B, s);
     }
   }) * 1000.0 / reps / NL;
   *bytes = by / NL;

@@ -172,6 +172,12 @@ struct SeqRow {
 struct AttnBlock {
   int tok0, n, slot, pos;
 };
+// A group of rows of a multi-sequence launch whose slots share K/V rows [0, len) with KV slot `slot` (their leader's):
+// rows[0..n) index the launch's SeqRow table
+struct ShareGroup {
+  int slot, len, n;
+  int rows[32];
+};
 struct PrefillQK {
   const float* qkv = nullptr;  // [T][qkv_stride]
   int qkv_stride = 0, k_off = 0, v_off = 0, n_head = 0, n_head_kv = 0, head_dim = 0;
@@ -214,6 +220,27 @@ struct PrefillAttn {
   const AttnBlock* blocks = nullptr;
   int n_blocks = 0;
 };
+// The shared-prefix form of the multi-sequence launch: K/V rows [0, len) of a group's members
+// are bit-equal to its leader slot's.  A first launch (grid.y = n_groups) runs the members' queries, one per MFMA
+// column, over the whole rounds below len on the leader's caches and leaves every wave's column state in sstate; the
+// multi-sequence launch then starts row b at round share_len[b] / (32 S) from that state (share_len[b]: the row's
+// group's len, 0 for a row outside every group).  Same bits as the unshared launch.  Its kernels take the launch's
+// arguments with these behind them (PrefillAttnShared), so the other forms' kernels are compiled as they were.
+struct AttnShare {
+  const ShareGroup* groups = nullptr;
+  int n_groups = 0;
+  const int32_t* share_len = nullptr;  // [rows]
+  float* sstate = nullptr;             // [row][head][ks][S] of SHARE_STATE(head_dim) floats: O^T column, m, l
+};
+struct PrefillAttnShared : PrefillAttn {
+  AttnShare sh;
+};
+constexpr int SHARE_STATE(int hd) { return hd + 4; }  // (16-byte slabs)
+// the fewest rows the host makes a group of: below it the groups' extra launch per layer costs more than the reads it
+// saves (4B shapes, 512- and 2048-token prompts: DESIGN.md section 19.5)
+constexpr int SHARE_MIN_ROWS = 24;
+// S, the key-split waves per work-group of the MFMA attention (launch_attn_mfma's table) for a head_dim and GQA group
+constexpr int prefill_attn_splits(int hd, int g) { return hd >= 256 ? 2 : (g == 4 && hd == 128) ? 2 : 4; }
 // the greedy batch loop's feedback (after the scorer's merge): a live row b takes id = argmax[b] -> out[b]; a stop id
 // ends the row (rows[b].pos = -1), any other id becomes tokens[b] at rows[b].pos + 1.  Ended rows: out[b] = -1
 struct BatchStops {
@@ -259,6 +286,8 @@ bool gemm_rows_supported(const DevWeight& w);
 void launch_gemm_rows(const PrefillGemm16& a, hipStream_t s);
 void launch_prefill_qk(const PrefillQK& a, int T, hipStream_t s);
 void launch_prefill_attn(const PrefillAttn& a, int T, hipStream_t s);
+// the multi-sequence form (a.rows) in its shared-prefix form: the groups' pass, the rows from its state, the merge
+void launch_prefill_attn_shared(const PrefillAttn& a, const AttnShare& sh, int T, hipStream_t s);
 void launch_prefill_gelu(const float* gu, int F, int H, XBlock* xq, int xstride, int T, hipStream_t s,
                          uint16_t* x16 = nullptr, int x16stride = 0, int q8k = 0, float* tscale = nullptr);
 

@@ -346,6 +346,12 @@ class Model:
         """llmi_session_seq_copy: K/V rows [0, n_pos) of every layer, slot src -> slot dst (moves or forks a prompt)."""
         check(lib().llmi_session_seq_copy(self.h, dst, src, n_pos))
 
+    def share_prefix(self, dst: int, src: int, n_pos: int) -> None:
+        """llmi_session_seq_share: copy_sequence, and the session remembers that rows [0, n_pos) of dst are src's --
+        batch_forward / batch_generate then read the rows a step's forked slots still share once per group of up to
+        32 rows.  Same bits; writing a row of either slot shortens the link to that row."""
+        check(lib().llmi_session_seq_share(self.h, dst, src, n_pos))
+
     def _batch_rows(self, tokens, slots, pos):
         t, sl, p = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (tokens, slots, pos))
         if not (t.size == sl.size == p.size):

@@ -12,6 +12,13 @@ row decodes at the same context.  After a warm-up of every loop:
       step's B rows) after each B's runs; what is left of the step is the GEMMs at T = B, the norms, the GELU and the
       q/k launch.
 Medians, with the min..max spread.  Prints one JSON line.
+
+    python scripts/bench_batch.py --shared [--prompts 512,2048] [--batches 8,32,64]
+
+The shared-prefix form: one prompt through forward(), Model.share_prefix into B - 1 further
+slots, then `steps` greedy steps of batch_generate over the B rows -- `repeats` times with the grouping on and, in the
+same process and interleaved, off (LLMI_BATCH_SHARED=0: the same rows through the unshared launches).  After each
+(prompt, B): time_kernel(16) (the shared form) and time_kernel(10) (the unshared form) over the last step's rows.
 """
 import argparse
 import json
@@ -28,6 +35,47 @@ def med(xs):
     return float(np.median(xs))
 
 
+def shared(a, cfg, g):
+    from llm_inference_amd.model import Model
+    batches = [int(b) for b in a.batches.split(",")]
+    rows = []
+    for P in [int(x) for x in a.prompts.split(",")]:
+        m = Model(g, max_ctx=P + a.steps + 8)
+        rng = np.random.default_rng(1)
+        prompt = np.concatenate([[2], rng.integers(4, cfg.vocab, P - 1)]).astype(np.int32)
+        m.forward(prompt, 0, want_logits=False)
+        first = m.last_argmax
+        m.reserve_sequences(max(batches))
+        for s in range(1, max(batches)):
+            m.share_prefix(s, 0, P)
+
+        def run(B, steps, on):
+            os.environ["LLMI_BATCH_SHARED"] = "1" if on else "0"
+            m.sync()
+            t0 = time.perf_counter()
+            m.batch_generate([first] * B, list(range(B)), [P] * B, steps)
+            return (time.perf_counter() - t0) / steps * 1e6
+
+        for B in batches:
+            run(B, a.warmup, True), run(B, a.warmup, False)
+            on, off = [], []
+            for _ in range(a.repeats):
+                off.append(run(B, a.steps, False))
+                on.append(run(B, a.steps, True))
+            us16, by16 = m.time_kernel(16, a.kernel_reps)
+            us10, by10 = m.time_kernel(10, a.kernel_reps)
+            rows.append({"prompt": P, "B": B,
+                         "step_us_shared": round(med(on), 1), "step_us_shared_min_max": [round(min(on), 1), round(max(on), 1)],
+                         "step_us_unshared": round(med(off), 1),
+                         "step_us_unshared_min_max": [round(min(off), 1), round(max(off), 1)],
+                         "attn_us_per_layer_shared": round(us16, 2), "attn_us_per_layer_unshared": round(us10, 2),
+                         "attn_kv_bytes_shared": by16, "attn_kv_bytes_unshared": by10,
+                         "attn_speedup": round(us10 / max(us16, 1e-9), 2), "step_speedup": round(med(off) / med(on), 3)})
+        m.close()
+    os.environ.pop("LLMI_BATCH_SHARED", None)
+    print(json.dumps({"config": cfg.name, "mode": "shared", "steps": a.steps, "repeats": a.repeats, "rows": rows}))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--config", default="gemma-3-4b")
@@ -36,13 +84,18 @@ def main():
     p.add_argument("--warmup", type=int, default=8)
     p.add_argument("--repeats", type=int, default=5)
     p.add_argument("--kernel-reps", type=int, default=20)
-    p.add_argument("--batches", default="1,2,4,8,16,32,64")
+    p.add_argument("--batches", default=None)
+    p.add_argument("--shared", action="store_true")
+    p.add_argument("--prompts", default="512,2048")
     a = p.parse_args()
+    a.batches = a.batches or ("8,32,64" if a.shared else "1,2,4,8,16,32,64")
     from llm_inference_amd.model import Model
     from llm_inference_amd.synthetic import CONFIGS, build_gemma3_gguf
     cfg = CONFIGS[a.config]
     batches = [int(b) for b in a.batches.split(",")]
     g = build_gemma3_gguf(cfg, seed=1234)
+    if a.shared:
+        return shared(a, cfg, g)
     m = Model(g, max_ctx=a.prefill + a.steps + 8)
     rng = np.random.default_rng(1)
     prompt = np.concatenate([[2], rng.integers(4, cfg.vocab, a.prefill - 1)]).astype(np.int32)
