@@ -51,6 +51,10 @@ typedef enum {
                               one-shot peer push (llmi_session_peer_connect) instead of RCCL */
 #define LLMI_EXACT_KQ 8u   /* session, with LLMI_EXACT only: the exact-order engine also takes K-quant (Q4_K / Q6_K)
                               layers; opt-in, also set by LLMI_EXACT_KQ=1 in the environment at session creation */
+#define LLMI_BATCH_QTABLE 16u /* session: batch steps also on a Q8_0 output table (multi-row int8 logits GEMV + f64 rows
+                                 reduce in place of the fused scorer); opt-in, also set by
+                                 LLMI_BATCH_QTABLE=1 in the environment at session creation.  No effect on a session
+                                 with an F16 table */
 
 const char* llmi_last_error(void);
 int llmi_version(void);
@@ -111,7 +115,7 @@ typedef struct llmi_tp_group llmi_tp_group;
 
 typedef struct {
   int device;          /* HIP device ordinal */
-  uint32_t flags;      /* LLMI_EXACT | LLMI_NO_GRAPH | LLMI_TP_PEER | LLMI_EXACT_KQ */
+  uint32_t flags;      /* LLMI_EXACT | LLMI_NO_GRAPH | LLMI_TP_PEER | LLMI_EXACT_KQ | LLMI_BATCH_QTABLE */
   int max_ctx;         /* KV-cache capacity in positions (default 4096) */
   int attn_split;      /* fast attention key-range splits: 0 = default (32, the only value) */
   /* Row-sharded tensor parallelism (north star: "weights shard row-wise across
@@ -436,6 +440,14 @@ int llmi_lookup_draft(const int32_t* hist, int L, int ngram_max, int ngram_min, 
  * that share one read of the table at width E (0: E is not supported). */
 int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap, float* logits);
 int llmi_logits_rows_rb(int E);
+
+/* op level, host pointers, synchronous: the multi-row Q8_0 x Q8_0 logits GEMV alone.  x: [T][E]
+ * f32 rows, each quantized on the device to Q8_0 blocks as the fast llmi_mat_vec_mul quantizes its x; wq: V rows of
+ * GGUF Q8_0 blocks ([V][E / 32][34 B]); logits: [T][V], softcap <= 0: none.  logits[t] carries the bits of the fast
+ * Q8_0 llmi_mat_vec_mul of wq with row t.  E % 32 == 0 and E <= 10912, else LLMI_E_SIZE.  llmi_logits_rows_q8_rb: the
+ * rows that share one read of the table at width E (0: E is not supported). */
+int llmi_logits_rows_q8(const float* x, const void* wq, int T, int V, int E, float softcap, float* logits);
+int llmi_logits_rows_q8_rb(int E);
 
 /* op level, host pointers, synchronous: out[t][n] = tscale[t] * sum_k f16(d (q - 8))[n][k] x16[t][k], the f16 x Q4_0
  * GEMM of the batch steps and the f16 prefill.  w_blocks: Q4_0 blocks in GGUF form

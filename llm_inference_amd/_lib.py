@@ -19,6 +19,7 @@ LLMI_EXACT = 1
 LLMI_NO_GRAPH = 2
 LLMI_TP_PEER = 4
 LLMI_EXACT_KQ = 8  # with LLMI_EXACT: the exact-order engine also takes K-quant layers
+LLMI_BATCH_QTABLE = 16  # batch steps also on a Q8_0 output table
 PEER_HANDLE_BYTES = 64
 
 STATUS = {0: "OK", 1: "E_SIZE", 2: "E_TYPE", 3: "E_ARG", 4: "E_HIP", 5: "E_GGUF", 6: "E_NODEV", 7: "E_RANGE"}
@@ -144,6 +145,8 @@ _SIGS = {
                                     C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "llmi_logits_rows": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp]),
     "llmi_logits_rows_rb": (C.c_int, [C.c_int]),
+    "llmi_logits_rows_q8": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _f32, _vp]),
+    "llmi_logits_rows_q8_rb": (C.c_int, [C.c_int]),
     "llmi_gemm_rows_f16": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int]),
     "llmi_gemm_rows_plan": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "llmi_gemm_rows_i8": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int]),

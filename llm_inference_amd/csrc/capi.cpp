@@ -824,6 +824,42 @@ int llmi_logits_rows(const uint16_t* x16, const uint16_t* w16, int T, int V, int
   });
 }
 
+int llmi_logits_rows_q8_rb(int E) { return logits_rows_q8_rb(E); }
+
+int llmi_logits_rows_q8(const float* x, const void* wq, int T, int V, int E, float softcap, float* logits) {
+  return guard([&] {
+    if (!x || !wq || !logits) throw status_error(LLMI_E_ARG, "logits_rows_q8: null pointer");
+    if (T <= 0 || V <= 0) throw status_error(LLMI_E_ARG, "logits_rows_q8: T and V must be positive");
+    if (logits_rows_q8_rb(E) == 0)
+      throw status_error(LLMI_E_SIZE, "logits_rows_q8: E must be a multiple of 32, at most 10912");
+    if ((long long)T * V > (long long)INT32_MAX) throw status_error(LLMI_E_SIZE, "logits_rows_q8: T x V too large");
+    if ((long long)T * E > (long long)INT32_MAX) throw status_error(LLMI_E_SIZE, "logits_rows_q8: T x E too large");
+    Ctx& c = ctx();
+    DevWeight w = alloc_weight(T_Q8_0, V, E);
+    try {
+      upload_rows(w, 0, wq, V, c.stream);
+      const int nb = E / 32;
+      const size_t xb = (size_t)T * E * 4, ob = (size_t)T * V * 4;
+      float* xd = (float*)c.get(0, xb);
+      float* od = (float*)c.get(1, ob);
+      Q8Act q;  // the T rows' Q8_0 blocks, row after row
+      q.xb = (XBlock*)c.get(10, ((size_t)T * nb + 1) * sizeof(XBlock));
+      q.nb = T * nb;
+      LLMI_HIP(hipMemcpyAsync(xd, x, xb, hipMemcpyHostToDevice, c.stream));
+      launch_quantize_q8_0(xd, T * E, q, c.stream);
+      launch_gemv_q8_0_rows(w, q.xb, nb, T, od, c.stream);
+      if (softcap > 0.0f) launch_softcap(od, T * V, softcap, c.stream);
+      LLMI_HIP(hipMemcpyAsync(logits, od, ob, hipMemcpyDeviceToHost, c.stream));
+      LLMI_HIP(hipStreamSynchronize(c.stream));
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      free_weight(w);
+      throw;
+    }
+    free_weight(w);
+  });
+}
+
 // llmi_score_rows (top_n = 0) and llmi_score_rows_top
 static int score_rows_impl(const uint16_t* x16, const uint16_t* w16, int T, int V, int E, float softcap,
                            const int32_t* targets, float* logprob, float* lse, int32_t* argmax, int top_n,

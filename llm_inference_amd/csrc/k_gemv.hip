@@ -177,6 +177,113 @@ __global__ __launch_bounds__(256) void gemv_q8_0_fast(const int4* __restrict__ q
   rows_out<R>(acc, lane, row0, nrows, out);
 }
 
+// gemv_q8_0_fast for several activation rows: the weight side is that kernel's -- the wave's R
+// table rows as one flat (row, block) list, lane L taking the items f = L (mod 64) in ascending order, the same ld_nt
+// loads -- and every item held in registers is applied to the RB activation rows of the work-group's row block
+// (blockIdx.y), whose XBlocks (prepare_act's, 48 B) wait in LDS.  Per activation row the arithmetic IS the fast
+// kernel's: the exact integer block dot, the term (sw * dx) * (float)dot added by acc_add<R> in item order, the same
+// rows_out -- so out[t][row] carries the bits launch_gemv(GEMV_FAST) writes for activation row t alone.  P only
+// batches loads: the next chunk of 64 P items is in flight while the current one is applied to the rows.  The table is
+// read once per row block.  T: the activation rows; idx non-null (the gathered form): output row t reads activation
+// row idx[t].
+template <int R, int P, int RB>
+__device__ __forceinline__ void gemv_q8_0_rows_body(const int4* __restrict__ qs, const uint16_t* __restrict__ wd,
+                                                    int rows, int nb, uint32_t magic, const uint4* __restrict__ xq,
+                                                    int xstride4, const int32_t* __restrict__ idx, int T,
+                                                    float* __restrict__ out) {
+  extern __shared__ uint4 xq_s[];  // [RB][nb] XBlocks, 3 uint4 each
+  const int lane = threadIdx.x & 63;
+  const int r0 = blockIdx.y * RB;
+  const int nr = min(RB, T - r0);
+  const int ru4 = nb * 3;
+  for (int i = threadIdx.x; i < nr * ru4; i += 256) {
+    const int r = i / ru4;
+    const int xrow = idx ? idx[r0 + r] : r0 + r;
+    xq_s[i] = xq[(size_t)xrow * xstride4 + (i - r * ru4)];
+  }
+  __syncthreads();
+  const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
+  if (row0 >= rows) return;
+  const int nrows = min(R, rows - row0);
+  const int total = nrows * nb;
+  const int4* qw = qs + (size_t)row0 * nb * 2;
+  const uint16_t* dw = wd + (size_t)row0 * nb;
+  float acc[RB][R];
+#pragma unroll
+  for (int r = 0; r < RB; r++)
+#pragma unroll
+    for (int k = 0; k < R; k++) acc[r][k] = 0.0f;
+  struct Chunk {
+    int4 w0[P], w1[P];
+    uint16_t d[P];
+    int rr[P], bb[P];
+  };
+  auto load = [&](Chunk& c, int c0) {
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+      const int f = c0 + p * 64 + lane;
+      const int fc = f < total ? f : 0;
+      const int r = div_by_magic(fc, magic);
+      c.rr[p] = f < total ? r : R;
+      c.bb[p] = fc - r * nb;
+      c.w0[p] = ld_nt(qw + 2 * fc);
+      c.w1[p] = ld_nt(qw + 2 * fc + 1);
+      c.d[p] = ld_nt16(dw + fc);
+    }
+  };
+  Chunk cur;
+  load(cur, 0);
+  for (int c0 = 0; c0 < total; c0 += 64 * P) {
+    Chunk nxt = cur;
+    if (c0 + 64 * P < total) load(nxt, c0 + 64 * P);  // (uniform over the wave)
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+      const float sw = h2f(cur.d[p]);
+      const uint4* xb = xq_s + cur.bb[p] * 3;
+#pragma unroll
+      for (int r = 0; r < RB; r++) {
+        if (r < nr) {  // (uniform over the work-group)
+          const int4* xp = reinterpret_cast<const int4*>(xb + r * ru4);
+          const int4 x0 = xp[0], x1 = xp[1];
+          const float dx = reinterpret_cast<const float*>(xp + 2)[0];
+          int dot = sdot4(cur.w0[p].x, x0.x, 0);
+          dot = sdot4(cur.w0[p].y, x0.y, dot); dot = sdot4(cur.w0[p].z, x0.z, dot); dot = sdot4(cur.w0[p].w, x0.w, dot);
+          dot = sdot4(cur.w1[p].x, x1.x, dot); dot = sdot4(cur.w1[p].y, x1.y, dot); dot = sdot4(cur.w1[p].z, x1.z, dot);
+          dot = sdot4(cur.w1[p].w, x1.w, dot);
+          acc_add<R>(acc[r], cur.rr[p], (sw * dx) * (float)dot);
+        }
+      }
+    }
+    cur = nxt;
+  }
+#pragma unroll
+  for (int r = 0; r < RB; r++)
+    if (r < nr) rows_out<R>(acc[r], lane, row0, nrows, out + (size_t)(r0 + r) * rows);
+}
+
+template <int R, int P, int RB>
+__global__ __launch_bounds__(256) void gemv_q8_0_rows_multi(const int4* __restrict__ qs, const uint16_t* __restrict__ wd,
+                                                            int rows, int nb, uint32_t magic,
+                                                            const uint4* __restrict__ xq, int xstride4, int T,
+                                                            float* __restrict__ out) {
+  gemv_q8_0_rows_body<R, P, RB>(qs, wd, rows, nb, magic, xq, xstride4, nullptr, T, out);
+}
+
+// The gathered form, as gemv_f16_rows_gather: compact rows base .. base + cap - 1 of a device list of *n_live
+// activation-row indices (idx points at entry `base`), out [cap][rows].  The rows at and past the count are not
+// written, and a work-group whose row block lies wholly there returns before it loads anything.
+template <int R, int P, int RB>
+__global__ __launch_bounds__(256) void gemv_q8_0_rows_gather(const int4* __restrict__ qs,
+                                                             const uint16_t* __restrict__ wd, int rows, int nb,
+                                                             uint32_t magic, const uint4* __restrict__ xq, int xstride4,
+                                                             const int32_t* __restrict__ idx,
+                                                             const int32_t* __restrict__ n_live, int base, int cap,
+                                                             float* __restrict__ out) {
+  const int T = min(cap, *n_live - base);
+  if ((int)blockIdx.y * RB >= T) return;
+  gemv_q8_0_rows_body<R, P, RB>(qs, wd, rows, nb, magic, xq, xstride4, idx, T, out);
+}
+
 // ===========================================================================
 // F16 (logits)
 // ===========================================================================
@@ -960,6 +1067,52 @@ void launch_gemv_f16_rows_gather(const DevWeight& w, const uint16_t* x16, int xs
 #undef LLMI_F16M
   }
   LLMI_HIP(hipGetLastError());
+}
+
+// R is launch_gemv's for the table (the bit contract); P = 2: two chunks of 128 items are in registers at a time
+// beside RB x R accumulators.  idx null: the plain form over T rows; else the gathered form over cap rows.
+static void launch_q8_0_rows(const DevWeight& w, const XBlock* xq, int xstride, const int32_t* idx,
+                             const int32_t* n_live, int base, int T, float* out, hipStream_t s) {
+  const int rb = logits_rows_q8_rb(w.cols);
+  if (w.type != T_Q8_0 || w.slab || rb == 0)
+    throw std::runtime_error("gemv_q8_0_rows: a Q8_0 table with cols % 32 == 0 and cols <= 10912");
+  const int rows = w.rows, nb = w.cols / 32;
+  if (xstride < nb) throw std::runtime_error("gemv_q8_0_rows: x row stride");
+  if (idx && (!n_live || base < 0)) throw std::runtime_error("gemv_q8_0_rows: the device list");
+  if (rows == 0 || T <= 0) return;
+  const int R = rows_per_wave(nb, rows);
+  const dim3 grid((rows + 4 * R - 1) / (4 * R), (T + rb - 1) / rb);
+  const size_t lds = (size_t)rb * nb * sizeof(XBlock);
+  const uint32_t mg = div_magic(nb);
+  const int4* qs = (const int4*)w.qs;
+  const uint4* x4 = (const uint4*)xq;
+  switch (R * 32 + rb) {
+#define LLMI_Q8M(RR, RBB)                                                                                          \
+  case RR * 32 + RBB:                                                                                              \
+    if (idx)                                                                                                       \
+      hipLaunchKernelGGL((gemv_q8_0_rows_gather<RR, 2, RBB>), grid, dim3(256), lds, s, qs, w.d, rows, nb, mg, x4,  \
+                         xstride * 3, idx, n_live, base, T, out);                                                  \
+    else                                                                                                           \
+      hipLaunchKernelGGL((gemv_q8_0_rows_multi<RR, 2, RBB>), grid, dim3(256), lds, s, qs, w.d, rows, nb, mg, x4,   \
+                         xstride * 3, T, out);                                                                     \
+    break;
+#define LLMI_Q8M3(RR) LLMI_Q8M(RR, 16) LLMI_Q8M(RR, 8) LLMI_Q8M(RR, 4)
+    LLMI_Q8M3(1) LLMI_Q8M3(2) LLMI_Q8M3(4) LLMI_Q8M3(8)
+#undef LLMI_Q8M3
+#undef LLMI_Q8M
+    default: throw std::runtime_error("gemv_q8_0_rows: no kernel for R/RB");
+  }
+  LLMI_HIP(hipGetLastError());
+}
+
+void launch_gemv_q8_0_rows(const DevWeight& w, const XBlock* xq, int xstride, int T, float* out, hipStream_t s) {
+  launch_q8_0_rows(w, xq, xstride, nullptr, nullptr, 0, T, out, s);
+}
+
+void launch_gemv_q8_0_rows_gather(const DevWeight& w, const XBlock* xq, int xstride, const int32_t* idx,
+                                  const int32_t* n_live, int base, int cap, float* out, hipStream_t s) {
+  if (!idx) throw std::runtime_error("gemv_q8_0_rows: the device list");
+  launch_q8_0_rows(w, xq, xstride, idx, n_live, base, cap, out, s);
 }
 
 }  // namespace llmi

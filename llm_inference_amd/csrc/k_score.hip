@@ -199,10 +199,9 @@ __global__ __launch_bounds__(256) void score_merge_kernel(ScoreArgs a, int n_vt)
   }
 }
 
-// Row path: one f32 logits row (forward's, after the soft-cap)
-__global__ __launch_bounds__(1024) void score_reduce_row_kernel(const float* __restrict__ x, int n, int target,
-                                                                float* logprob, float* lse, int32_t* argmax,
-                                                                double* lse64) {
+// Row path: one f32 logits row (forward's, after the soft-cap), by one work-group of 1024 threads
+__device__ __forceinline__ void score_reduce_row_body(const float* __restrict__ x, int n, int target, float* logprob,
+                                                      float* lse, int32_t* argmax, double* lse64) {
   __shared__ double sh[1024];
   __shared__ float s_mx[1024];
   __shared__ unsigned long long s_key[1024];
@@ -243,6 +242,22 @@ __global__ __launch_bounds__(1024) void score_reduce_row_kernel(const float* __r
   }
 }
 
+__global__ __launch_bounds__(1024) void score_reduce_row_kernel(const float* __restrict__ x, int n, int target,
+                                                                float* logprob, float* lse, int32_t* argmax,
+                                                                double* lse64) {
+  score_reduce_row_body(x, n, target, logprob, lse, argmax, lse64);
+}
+
+// The row path for the rows of x [gridDim.x][n], one work-group each: row r's chain is the one-row launch's, so its
+// lse / arg-max / log-prob carry that launch's bits.  targets null: no log-probs.
+__global__ __launch_bounds__(1024) void score_reduce_rows_kernel(const float* __restrict__ x, int n,
+                                                                 const int32_t* __restrict__ targets, float* logprob,
+                                                                 float* lse, int32_t* argmax) {
+  const int r = blockIdx.x;
+  score_reduce_row_body(x + (size_t)r * n, n, targets ? targets[r] : -1, logprob ? logprob + r : nullptr, lse + r,
+                        argmax + r, nullptr);
+}
+
 }  // namespace
 
 void launch_score_rows(const ScoreArgs& a, hipStream_t s) {
@@ -262,6 +277,14 @@ void launch_score_reduce_row(const float* logits, int V, int target, float* logp
   if (V < 1 || target >= V) throw std::runtime_error("score_reduce_row: target outside the row");
   hipLaunchKernelGGL(score_reduce_row_kernel, dim3(1), dim3(1024), 0, s, logits, V, target, logprob, lse, argmax,
                      lse64);
+  LLMI_HIP(hipGetLastError());
+}
+
+void launch_score_reduce_rows(const float* logits, int V, int n_rows, const int32_t* targets, float* logprob,
+                              float* lse, int32_t* argmax, hipStream_t s) {
+  if (V < 1 || n_rows < 1 || !lse || !argmax) throw std::runtime_error("score_reduce_rows: rows, V >= 1 and outputs");
+  hipLaunchKernelGGL(score_reduce_rows_kernel, dim3(n_rows), dim3(1024), 0, s, logits, V, targets, logprob, lse,
+                     argmax);
   LLMI_HIP(hipGetLastError());
 }
 

@@ -605,12 +605,16 @@ void launch_residual_norm(const float* y, const float* w_post, float* resid, con
 }
 
 // residual_norm_kernel<false> (post_scale 1, w_post set) per row blockIdx.x, the same expressions and the same
-// 1024-thread sums, so row i's f16 image equals the one-row launch's NormOut::x16 bit for bit; writes nothing else
+// 1024-thread sums, so row i's f16 image equals the one-row launch's NormOut::x16 bit for bit; writes nothing else.
+// Q8 (n % 32 == 0): the row's f32 image -- the one-row launch's NormOut::xn -- also as Q8_0 blocks xq[row][n / 32],
+// quantized as launch_quantize_q8_0 quantizes xn (a half-wave holds one block: element t + 1024 k of thread t)
+template <bool Q8>
 __global__ __launch_bounds__(1024) void residual_norm_rows16_kernel(const float* __restrict__ y, int ystride,
                                                                     const float* __restrict__ w_post,
                                                                     const float* __restrict__ resid, int rstride,
                                                                     const float* __restrict__ w_next,
-                                                                    uint16_t* __restrict__ x16, int xstride, int n,
+                                                                    uint16_t* __restrict__ x16, int xstride,
+                                                                    XBlock* __restrict__ xq, int qstride, int n,
                                                                     double eps) {
   __shared__ float sh[16];
   const int t = threadIdx.x;
@@ -638,7 +642,12 @@ __global__ __launch_bounds__(1024) void residual_norm_rows16_kernel(const float*
 #pragma unroll
   for (int k = 0; k < NORM_EPT; k++) {
     const int i = t + k * 1024;
-    if (i < n) x16[i] = f2h_ggml((sc2 * hv[k]) * wn[k]);
+    const float v = (sc2 * hv[k]) * wn[k];
+    if (i < n) x16[i] = f2h_ggml(v);
+    if constexpr (Q8) {
+      const bool ok = i < n;
+      q8_block_store(ok ? v : 0.0f, ok, xq + (size_t)blockIdx.x * qstride + (ok ? (i >> 5) : 0), i & 31);
+    }
   }
 }
 
@@ -647,8 +656,18 @@ void launch_residual_norm_rows16(const float* y, int ystride, const float* w_pos
                                  hipStream_t s) {
   if (n > 1024 * NORM_EPT) throw std::runtime_error("residual_norm: n_embd > 8192");
   if (T < 1 || !w_post) throw std::runtime_error("residual_norm_rows16: no rows / no post norm");
-  hipLaunchKernelGGL(residual_norm_rows16_kernel, dim3(T), dim3(1024), 0, s, y, ystride, w_post, resid, rstride, w_next,
-                     x16, xstride, n, eps);
+  hipLaunchKernelGGL(residual_norm_rows16_kernel<false>, dim3(T), dim3(1024), 0, s, y, ystride, w_post, resid, rstride,
+                     w_next, x16, xstride, nullptr, 0, n, eps);
+  LLMI_HIP(hipGetLastError());
+}
+
+void launch_residual_norm_rows16_q8(const float* y, int ystride, const float* w_post, const float* resid, int rstride,
+                                    const float* w_next, uint16_t* x16, int xstride, XBlock* xq, int qstride, int n,
+                                    int T, double eps, hipStream_t s) {
+  if (n > 1024 * NORM_EPT || n % 32 != 0) throw std::runtime_error("residual_norm_rows16_q8: n_embd % 32, <= 8192");
+  if (T < 1 || !w_post || !xq || qstride < n / 32) throw std::runtime_error("residual_norm_rows16_q8: rows / blocks");
+  hipLaunchKernelGGL(residual_norm_rows16_kernel<true>, dim3(T), dim3(1024), 0, s, y, ystride, w_post, resid, rstride,
+                     w_next, x16, xstride, xq, qstride, n, eps);
   LLMI_HIP(hipGetLastError());
 }
 

@@ -79,6 +79,21 @@ void launch_gemv_f16_rows(const DevWeight& w, const uint16_t* x16, int xstride, 
 void launch_gemv_f16_rows_gather(const DevWeight& w, const uint16_t* x16, int xstride, const int32_t* idx,
                                  const int32_t* n_live, int base, int cap, float* out, hipStream_t s);
 
+// The fast Q8_0 x Q8_0 GEMV for T activation rows at once: xq [T][xstride] XBlocks
+// (prepare_act's Q8_0 image of each row), out [T][w.rows] f32; out[t] carries the bits launch_gemv(GEMV_FAST) writes
+// for row t alone.  The table is read once per block of logits_rows_q8_rb(cols) activation rows, whose blocks wait in
+// at most 64 KB of LDS (48 B per 32 columns), with at most 16 x 8 accumulators per lane: 16 rows up to 2720 columns,
+// 8 up to 5440, 4 up to 10912; 0: the width is not supported.
+constexpr int logits_rows_q8_rb(int cols) {
+  return (cols <= 0 || cols % 32 != 0) ? 0 : cols / 32 * 48 * 16 <= 65536 ? 16 : cols / 32 * 48 * 8 <= 65536 ? 8
+         : cols / 32 * 48 * 4 <= 65536 ? 4 : 0;
+}
+void launch_gemv_q8_0_rows(const DevWeight& w, const XBlock* xq, int xstride, int T, float* out, hipStream_t s);
+// The gathered form, the arguments of launch_gemv_f16_rows_gather: out[i] (i < min(cap, *n_live - base)) carries the
+// bits launch_gemv(GEMV_FAST) writes for activation row idx[i] alone.
+void launch_gemv_q8_0_rows_gather(const DevWeight& w, const XBlock* xq, int xstride, const int32_t* idx,
+                                  const int32_t* n_live, int base, int cap, float* out, hipStream_t s);
+
 // elementwise / norms
 // o = rms_norm(x) [* w if w]  per row of n, n_rows rows; exact = serial FMA sum
 void launch_rms_norm(const float* x, const float* w, float* o, int n, int n_rows, double eps, bool exact,
@@ -131,6 +146,10 @@ void launch_score_top(const ScoreArgs& a, hipStream_t s);
 // logprob[0] / lse[0] / argmax[0]; target -1: none.  lse64 (may be null): the f64 log-sum-exp before its rounding.
 void launch_score_reduce_row(const float* logits, int V, int target, float* logprob, float* lse, int32_t* argmax,
                              hipStream_t s, double* lse64 = nullptr);
+// The row path for n_rows rows of logits [n_rows][V] in one launch: row r's lse[r] / argmax[r] (and logprob[r] of
+// targets[r], when both pointers are set; -1: none) carry the bits of launch_score_reduce_row on that row.
+void launch_score_reduce_rows(const float* logits, int V, int n_rows, const int32_t* targets, float* logprob,
+                              float* lse, int32_t* argmax, hipStream_t s);
 // Row path's top-N: top_id / top_lp [top_n] of one f32 logits row, the fused pass's rule; lse64: the reduce's.
 void launch_score_top_row(const float* logits, int V, int top_n, const double* lse64, int32_t* top_id, float* top_lp,
                           hipStream_t s);

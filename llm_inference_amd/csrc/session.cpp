@@ -515,6 +515,8 @@ Session::Session(const uint8_t* gguf, size_t size, const llmi_session_opts& opts
   exact_ = (opts.flags & LLMI_EXACT) != 0;
   exact_kq_ = exact_ && (opts.flags & LLMI_EXACT_KQ) != 0;
   if (const char* e = getenv("LLMI_EXACT_KQ")) exact_kq_ = exact_kq_ || (exact_ && atoi(e) != 0);
+  batch_qtable_ = (opts.flags & LLMI_BATCH_QTABLE) != 0;
+  if (const char* e = getenv("LLMI_BATCH_QTABLE")) batch_qtable_ = batch_qtable_ || atoi(e) != 0;
   ex_gemv_ = ex_norm_ = ex_attn_ = ex_logits_ = exact_;
   if (const char* e = getenv("LLMI_EXACT_PARTS")) {  // diagnostics: mix exact/fast kernel families
     const std::string s(e);
@@ -1942,6 +1944,12 @@ int Session::score_path() const {
   const bool fused = !exact_ && prefill_ok_ && getenv("LLMI_NO_PREFILL") == nullptr && embd_.type == T_F16 &&
                      hp_.n_embd % 16 == 0 && !ple_table_.qs;
   return fused ? 1 : 2;
+}
+
+bool Session::batch_steps_ok() const {
+  if (!qtable_steps()) return score_path() == 1;
+  return !tp_ && !exact_ && prefill_ok_ && getenv("LLMI_NO_PREFILL") == nullptr && hp_.n_embd % 16 == 0 &&
+         !ple_table_.qs;
 }
 
 void Session::ensure_score_buffers(int cap) {

@@ -429,7 +429,8 @@ class Session {
   // final-norm rows sc_x16_[0..B) -> bt_logits_ [B][vocab], soft-capped: the multi-row logits GEMV, or launch_gemv
   // row by row for a table width it does not take
   // (x16: the rows to read instead of sc_x16_ -- batch_extend's compact block)
-  void batch_logits(int B, hipStream_t s, const uint16_t* x16 = nullptr);
+  // (q_row0: with qtable_steps(), the same rows' first row in bq_xq_)
+  void batch_logits(int B, hipStream_t s, const uint16_t* x16 = nullptr, int q_row0 = 0);
   SamplerDev* bt_samplers_ = nullptr;         // [LLMI_SEQ_MAX] the sampled loop's per-row samplers
   float* bt_logits_ = nullptr;                // [bt_logits_cap_][vocab] grow-only
   unsigned long long* bt_surv_ = nullptr;     // [bt_logits_cap_][SAMPLE_MAX_GROUPS x 256]
@@ -439,6 +440,24 @@ class Session {
   int bt_samp_B_ = 0;                         // rows of the most recent sampled batch step (time_kernel(11))
   std::vector<SeqRow> bt_samp_rows_;          // ... as it ran them
   void ensure_batch_logits(int B, bool surv);
+  // batch steps on a Q8_0 output table (LLMI_BATCH_QTABLE): no fused scorer -- a step's output
+  // rows go through the multi-row int8 logits GEMV and the f64 rows reduce, LLMI_SEQ_MAX rows at a time
+  bool batch_qtable_ = false;
+  bool qtable_steps() const {
+    return batch_qtable_ && embd_.type == T_Q8_0 && logits_w_.type == T_Q8_0 && hp_.n_embd % 32 == 0;
+  }
+  // what the batch entry points ask of the session: score_path() == 1 on an F16 table; with qtable_steps() the same
+  // conditions without the table's type
+  bool batch_steps_ok() const;
+  XBlock* bq_xq_ = nullptr;    // [LLMI_BATCH_TOKENS_MAX][n_embd / 32] the step's output rows as Q8_0 blocks (step_tail)
+  XBlock* bq_row0_ = nullptr;  // [LLMI_SEQ_MAX][n_embd / 32] position-0 rows' blocks (batch_row0)
+  // rows q_row0 .. q_row0 + n - 1 of bq_xq_ -> bt_logits_ [n][vocab], soft-capped (n <= LLMI_SEQ_MAX): the multi-row
+  // launch from QTABLE_ROWS_MIN rows on, below it one launch_gemv per row; LLMI_BATCH_QTABLE_ROWS (read at the call):
+  // 0 = always per row, N > 0 = the multi-row launch from N rows on.  Returns whether the multi-row launch ran.
+  bool qtable_logits(int q_row0, int n, hipStream_t s);
+  // ... then their lse / arg-max into sc_lse_ / sc_amax_ at o0: one rows launch, or (per-row form) one launch per row
+  void qtable_reduce(int o0, int n, bool multi, hipStream_t s);
+  int logits_rb() const { return qtable_steps() ? logits_rows_q8_rb(hp_.n_embd) : logits_rows_rb(hp_.n_embd); }
   void time_batch_sampling(int reps, double* us, double* bytes);
   // ragged batch steps (llmi_session_batch_extend): a step is a list of spans, its token rows
   // the spans concatenated

@@ -33,9 +33,10 @@ void Session::seq_reserve(int n_seq) {
                                      "2 or 4");
   if (!prefill_ok_) throw status_error(LLMI_E_ARG, "seq_reserve: the session has no batched prefill");
   if (getenv("LLMI_NO_PREFILL")) throw status_error(LLMI_E_ARG, "seq_reserve: the batched prefill is off (LLMI_NO_PREFILL)");
-  if (embd_.type != T_F16)
+  // (LLMI_BATCH_QTABLE on a Q8_0 table: the multi-row int8 logits GEMV and the rows reduce take the scorer's place)
+  if (embd_.type != T_F16 && !qtable_steps())
     throw status_error(LLMI_E_ARG, "seq_reserve: needs the fused scorer, i.e. an F16 output table (this one is quantized)");
-  if (score_path() != 1) throw status_error(LLMI_E_ARG, "seq_reserve: needs the fused scorer (score_path 1)");
+  if (!batch_steps_ok()) throw status_error(LLMI_E_ARG, "seq_reserve: needs the fused scorer (score_path 1)");
   if (n_seq < 1 || n_seq > LLMI_SEQ_MAX)
     throw status_error(LLMI_E_RANGE, "seq_reserve: n_seq must be in 1.." + std::to_string(LLMI_SEQ_MAX));
   ensure_usable();
@@ -53,6 +54,11 @@ void Session::seq_reserve(int n_seq) {
     bt_row0_ = dalloc<uint16_t>((size_t)LLMI_SEQ_MAX * hp_.n_embd);
     bt_r0_lse_ = dalloc<float>(2 * LLMI_SEQ_MAX);
     bt_r0_amax_ = dalloc<int32_t>(LLMI_SEQ_MAX);
+    if (qtable_steps()) {
+      bq_xq_ = dalloc<XBlock>((size_t)LLMI_BATCH_TOKENS_MAX * (hp_.n_embd / 32));
+      bq_row0_ = dalloc<XBlock>((size_t)LLMI_SEQ_MAX * (hp_.n_embd / 32));
+      ensure_batch_logits(LLMI_SEQ_MAX, false);  // (step_tail's chunks: no allocation between a loop's launches)
+    }
     for (int q = 0; q < LLMI_SEQ_MAX; q++) sh_leader_[q] = q, sh_n_[q] = 0;
   }
   // the slots below n_seq that have no cache yet: their own allocations (zeroed on the stream), so a larger reserve
@@ -145,7 +151,7 @@ void Session::batch_check(const char* fn, const int32_t* tokens, const int32_t* 
                           int n_steps) const {
   const std::string f = std::string(fn) + ": ";
   if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
-  if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
+  if (!batch_steps_ok()) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
   if (B < 1 || B > n_seq_) throw status_error(LLMI_E_RANGE, f + "B must be in 1..n_seq (B)");
   if (n_steps < 0) throw status_error(LLMI_E_ARG, f + "negative step count (n_steps)");
   bool seen[LLMI_SEQ_MAX] = {};
@@ -213,6 +219,12 @@ void Session::batch_row0(int32_t token, int slot, int b) {
     record_step(stream_, false);  // STEP_LOGITS's launches
     launch_score_reduce_row(logits_, vocab_, -1, bt_r0_lse_ + LLMI_SEQ_MAX + b, bt_r0_lse_ + b, bt_r0_amax_ + b, stream_);
   }
+  if (qtable_steps()) {  // the step quantized xn_ for the table (record_logits): those blocks, and xn_'s f16 image
+    const size_t nb = (size_t)hp_.n_embd / 32;
+    LLMI_HIP(hipMemcpyAsync(bq_row0_ + (size_t)b * nb, act_.q8.xb, nb * sizeof(XBlock), hipMemcpyDeviceToDevice, stream_));
+    launch_round_f16(xn_, hp_.n_embd, dst, stream_);
+    return;
+  }
   LLMI_HIP(hipMemcpyAsync(dst, act_.x16, (size_t)hp_.n_embd * 2, hipMemcpyDeviceToDevice, stream_));
 }
 
@@ -222,18 +234,35 @@ void Session::ensure_batch_apart() {
 
 void Session::step_tail(uint16_t* x16, const OutRun* runs, size_t n_runs, const std::vector<OutRow0>& r0, bool score) {
   hipStream_t s = stream_;
-  const int E = hp_.n_embd;
+  const int E = hp_.n_embd, nb = E / 32;
+  const bool qt = qtable_steps();  // compact row o's Q8_0 blocks: row o of bq_xq_
   int n = 0;
   for (size_t i = 0; i < n_runs; i++) {
     const OutRun& o = runs[i];
-    launch_residual_norm_rows16(pf_out_ + (size_t)o.row0 * E, E, L_.back().post_ffw_norm, pf_resid_ + (size_t)o.row0 * E,
-                                E, out_norm_, x16 + (size_t)o.o0 * E, E, E, o.n, hp_.eps, s);
+    if (qt)
+      launch_residual_norm_rows16_q8(pf_out_ + (size_t)o.row0 * E, E, L_.back().post_ffw_norm,
+                                     pf_resid_ + (size_t)o.row0 * E, E, out_norm_, x16 + (size_t)o.o0 * E, E,
+                                     bq_xq_ + (size_t)o.o0 * nb, nb, E, o.n, hp_.eps, s);
+    else
+      launch_residual_norm_rows16(pf_out_ + (size_t)o.row0 * E, E, L_.back().post_ffw_norm,
+                                  pf_resid_ + (size_t)o.row0 * E, E, out_norm_, x16 + (size_t)o.o0 * E, E, E, o.n, hp_.eps, s);
     n += o.n;
   }
-  for (const OutRow0& p : r0)
+  for (const OutRow0& p : r0) {
     LLMI_HIP(hipMemcpyAsync(x16 + (size_t)p.o * E, bt_row0_ + (size_t)p.k * E, (size_t)E * 2, hipMemcpyDeviceToDevice, s));
+    if (qt)
+      LLMI_HIP(hipMemcpyAsync(bq_xq_ + (size_t)p.o * nb, bq_row0_ + (size_t)p.k * nb, (size_t)nb * sizeof(XBlock),
+                              hipMemcpyDeviceToDevice, s));
+  }
   if (!score) return;
-  launch_score_rows(score_args(x16, n, nullptr), s);
+  if (qt) {  // forward's logits of LLMI_SEQ_MAX rows at a time (bt_logits_), each row reduced in f64 as score's path 2
+    for (int c0 = 0; c0 < n; c0 += LLMI_SEQ_MAX) {
+      const int cn = std::min(LLMI_SEQ_MAX, n - c0);
+      qtable_reduce(c0, cn, qtable_logits(c0, cn, s), s);
+    }
+  } else {
+    launch_score_rows(score_args(x16, n, nullptr), s);
+  }
   for (const OutRow0& p : r0) {  // (batch_row0)
     if (!p.single) continue;
     LLMI_HIP(hipMemcpyAsync(sc_lse_ + p.o, bt_r0_lse_ + p.k, 4, hipMemcpyDeviceToDevice, s));
@@ -362,7 +391,7 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
                            float* lse) {
   const std::string f = "batch_extend: ";
   if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
-  if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
+  if (!batch_steps_ok()) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
   if (n_spans < 1 || n_spans > n_seq_) throw status_error(LLMI_E_RANGE, f + "n_spans must be in 1..n_seq (n_spans)");
   bool seen[LLMI_SEQ_MAX] = {};
   int total = 0, n_out_all = 0;
@@ -464,7 +493,7 @@ void Session::batch_extend(const int32_t* tokens, const llmi_span* spans, int n_
       for (const OutRun& o : outs)
         for (int c0 = 0; c0 < o.n; c0 += LLMI_SEQ_MAX) {
           const int n = std::min(LLMI_SEQ_MAX, o.n - c0);
-          batch_logits(n, s, bx_x16_ + (size_t)(o.o0 + c0) * E);
+          batch_logits(n, s, bx_x16_ + (size_t)(o.o0 + c0) * E, o.o0 + c0);
           LLMI_HIP(hipMemcpyAsync(logits + (size_t)(o.dst + c0) * vocab_, bt_logits_, (size_t)n * vocab_ * 4,
                                   hipMemcpyDeviceToHost, s));
         }
@@ -507,8 +536,43 @@ void Session::ensure_batch_logits(int B, bool surv) {  // grow-only, as the pref
   }
 }
 
-void Session::batch_logits(int B, hipStream_t s, const uint16_t* x16) {
+// whether a launch of n rows takes the multi-row form (LLMI_BATCH_QTABLE_ROWS, read at the call: 0 = never, N > 0 =
+// from N rows on)
+static bool qtable_multi(int n, int n_embd) {
+  int min_rows = QTABLE_ROWS_MIN;
+  if (const char* c = getenv("LLMI_BATCH_QTABLE_ROWS")) min_rows = atoi(c);
+  return min_rows > 0 && n >= min_rows && logits_rows_q8_rb(n_embd) != 0;
+}
+
+bool Session::qtable_logits(int q_row0, int n, hipStream_t s) {
+  const int nb = hp_.n_embd / 32;
+  const bool multi = qtable_multi(n, hp_.n_embd);
+  if (multi) {
+    launch_gemv_q8_0_rows(logits_w_, bq_xq_ + (size_t)q_row0 * nb, nb, n, bt_logits_, s);
+  } else {  // one table read per row
+    for (int i = 0; i < n; i++) {
+      ActBuf a;
+      a.q8.xb = bq_xq_ + (size_t)(q_row0 + i) * nb;
+      a.q8.nb = nb;
+      launch_gemv(logits_w_, a, bt_logits_ + (size_t)i * vocab_, GEMV_FAST, s, nullptr);
+    }
+  }
+  if (hp_.final_softcap > 0.0f) launch_softcap(bt_logits_, n * vocab_, hp_.final_softcap, s);
+  return multi;
+}
+
+void Session::qtable_reduce(int o0, int n, bool multi, hipStream_t s) {
+  if (multi) return launch_score_reduce_rows(bt_logits_, vocab_, n, nullptr, nullptr, sc_lse_ + o0, sc_amax_ + o0, s);
+  for (int i = 0; i < n; i++)
+    launch_score_reduce_row(bt_logits_ + (size_t)i * vocab_, vocab_, -1, nullptr, sc_lse_ + o0 + i, sc_amax_ + o0 + i, s);
+}
+
+void Session::batch_logits(int B, hipStream_t s, const uint16_t* x16, int q_row0) {
   const int E = hp_.n_embd;
+  if (qtable_steps()) {
+    qtable_logits(q_row0, B, s);
+    return;
+  }
   if (!x16) x16 = sc_x16_;
   if (logits_rows_rb(E) != 0) {
     launch_gemv_f16_rows(logits_w_, x16, E, B, bt_logits_, s);
@@ -653,10 +717,13 @@ void Session::lookup_select(const SeqRow* trows, int T, int W, bool gather, bool
   for (int c0 = 0; c0 < T; c0 += LLMI_SEQ_MAX) {
     const int n = std::min(LLMI_SEQ_MAX, T - c0);
     if (gather) {
-      launch_gemv_f16_rows_gather(logits_w_, sc_x16_, E, live + c0, la.n_live, c0, n, bt_logits_, s);
+      if (qtable_steps())
+        launch_gemv_q8_0_rows_gather(logits_w_, bq_xq_, E / 32, live + c0, la.n_live, c0, n, bt_logits_, s);
+      else
+        launch_gemv_f16_rows_gather(logits_w_, sc_x16_, E, live + c0, la.n_live, c0, n, bt_logits_, s);
       if (hp_.final_softcap > 0.0f) launch_softcap_live_rows(bt_logits_, vocab_, n, la.n_live, c0, hp_.final_softcap, s);
     } else {  // every token row, listed or not (the list is the identity)
-      batch_logits(n, s, sc_x16_ + (size_t)c0 * E);
+      batch_logits(n, s, sc_x16_ + (size_t)c0 * E, c0);
     }
     ta.idx = live + c0;
     ta.base = c0;
@@ -672,7 +739,7 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
                           llmi_lookup_stats* stats) {
   const std::string f = std::string(fn) + ": ";
   if (!seq_reserved_) throw status_error(LLMI_E_ARG, f + "no KV slots reserved (call seq_reserve first)");
-  if (score_path() != 1) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
+  if (!batch_steps_ok()) throw status_error(LLMI_E_ARG, f + "the batched prefill is off (LLMI_NO_PREFILL)");
   if (B < 1 || B > n_seq_) throw status_error(LLMI_E_RANGE, f + "B must be in 1..n_seq (B)");
   stop_ids(f, stop, n_stop, nullptr);  // (the ids' range is checked where it always was, below)
   if (lk.draft_len < 1 || lk.draft_len > LOOKUP_DRAFT_MAX)
@@ -720,7 +787,8 @@ void Session::lookup_loop(const char* fn, const int32_t* hist, const int32_t* hi
   // A/B, read at the call: the logits of every token row, without the list (also the table widths the multi-row
   // GEMV does not take, through batch_logits' row-by-row path)
   const char* ng_env = getenv("LLMI_LOOKUP_NO_GATHER");
-  const bool gather = !(ng_env && atoi(ng_env) == 1) && logits_rows_rb(hp_.n_embd) != 0;
+  bool gather = !(ng_env && atoi(ng_env) == 1) && logits_rb() != 0;
+  if (const char* c = getenv("LLMI_BATCH_QTABLE_ROWS")) gather = gather && !(qtable_steps() && atoi(c) == 0);
   ensure_usable();
   for (int b = 0; b < B; b++) share_write(slots[b], pos[b]);
   int group = 4;
@@ -873,7 +941,7 @@ void Session::time_lookup_select(int reps, double* us, double* bytes) {
   LLMI_HIP(hipMemcpyAsync(&n_live, lk_tlive_ + LLMI_BATCH_TOKENS_MAX, 4, hipMemcpyDeviceToHost, s));
   LLMI_HIP(hipStreamSynchronize(s));
   // table reads: one per block of RB listed rows; without the list one per block of every chunk's token rows
-  const int rb = logits_rows_rb(hp_.n_embd);
+  const int rb = logits_rb();
   int reads = 0;
   if (lk_samp_.gather) {
     reads = (n_live + rb - 1) / rb;
@@ -903,7 +971,7 @@ void Session::time_batch_sampling(int reps, double* us, double* bytes) {
   if (B == 0 || reps <= 0) return;
   hipStream_t s = stream_;
   h2d(bt_trows_, bt_samp_rows_.data(), (size_t)B * sizeof(SeqRow));
-  const int rb = logits_rows_rb(E);
+  const int rb = qtable_steps() && !qtable_multi(B, E) ? 0 : logits_rb();
   const BatchStops st{};
   *us = time_reps(s, reps, [&] {
     batch_logits(B, s);

@@ -49,6 +49,11 @@ void launch_residual_norm(const float* y, const float* w_post, float* resid, con
 void launch_residual_norm_rows16(const float* y, int ystride, const float* w_post, const float* resid, int rstride,
                                  const float* w_next, uint16_t* x16, int xstride, int n, int T, double eps,
                                  hipStream_t s);
+// batch steps on a Q8_0 output table: the same launch, which also leaves each row's f32 image
+// -- the one-row launch's NormOut::xn -- as Q8_0 blocks xq[row][qstride], launch_quantize_q8_0's bits (n % 32 == 0)
+void launch_residual_norm_rows16_q8(const float* y, int ystride, const float* w_post, const float* resid, int rstride,
+                                    const float* w_next, uint16_t* x16, int xstride, XBlock* xq, int qstride, int n,
+                                    int T, double eps, hipStream_t s);
 // Gemma-4 per-layer inputs (model.cpp:676-701): inp[l][i] = (rms(proj[l])[i] * nw[i] + inp[l][i]) / sqrt(2),
 // proj already scaled by 1/sqrt(n_embd); one work-group per layer
 void launch_ple_combine(const float* proj, const float* nw, float* inp, int n_layer, int n_epl, double eps, bool exact,
@@ -239,6 +244,9 @@ constexpr int SHARE_STATE(int hd) { return hd + 4; }  // (16-byte slabs)
 // the fewest rows the host makes a group of: below it the groups' extra launch per layer costs more than the reads it
 // saves (4B shapes, 512- and 2048-token prompts: DESIGN.md section 19.5)
 constexpr int SHARE_MIN_ROWS = 24;
+// batch steps on a Q8_0 output table: the fewest rows of a launch that take the multi-row logits GEMV and the rows
+// reduce; below it one launch_gemv and one row reduce per row (DESIGN.md section 20.5's measurements)
+constexpr int QTABLE_ROWS_MIN = 2;
 // S, the key-split waves per work-group of the MFMA attention (launch_attn_mfma's table) for a head_dim and GQA group
 constexpr int prefill_attn_splits(int hd, int g) { return hd >= 256 ? 2 : (g == 4 && hd == 128) ? 2 : 4; }
 // the greedy batch loop's feedback (after the scorer's merge): a live row b takes id = argmax[b] -> out[b]; a stop id

@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from ._lib import (BATCH_TOKENS_MAX, LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, SPAN_ALL,
+from ._lib import (BATCH_TOKENS_MAX, LLMI_BATCH_QTABLE, LLMI_EXACT, LLMI_EXACT_KQ, LLMI_NO_GRAPH, LLMI_TP_PEER, PEER_HANDLE_BYTES, SPAN_ALL,
                    SPAN_LAST, SPAN_NONE, TP_ID_BYTES, TRACE_FN, Lookup, LookupStats, Sampler, SessionInfo, SessionOpts,
                    Span, check, lib, ptr)
 from .gguf import GGUFFile
@@ -209,14 +209,18 @@ class Model:
     def __init__(self, gguf, device: int = 0, exact: bool = False, max_ctx: int = 4096,
                  use_graph: bool = True, attn_split: int = 0, tp_rank: int = 0, tp_size: int = 1,
                  tp_id: Optional[bytes] = None, tp_group: Optional["TPGroup"] = None, tp_peer: bool = False,
-                 exact_kq: bool = False):
+                 exact_kq: bool = False, batch_qtable: bool = False):
         """tp_id (RCCL, one process per GPU), tp_group (ranks on one device,
         one host thread each) or tp_peer (one process per GPU, the one-shot
         push exchange: peer_handle() / peer_connect() before the first
         forward) makes this session rank tp_rank of a row-sharded
         tensor-parallel group of tp_size (include/llmi.h).  exact_kq (with
         exact): K-quant layers run on the exact-order engine too
-        (LLMI_EXACT_KQ; the environment's LLMI_EXACT_KQ=1 does the same)."""
+        (LLMI_EXACT_KQ; the environment's LLMI_EXACT_KQ=1 does the same).
+        batch_qtable: batch steps (reserve_sequences and everything after
+        it) also on a Q8_0 output table (LLMI_BATCH_QTABLE; the
+        environment's LLMI_BATCH_QTABLE=1 does the same; DESIGN.md
+        section 20); nothing changes on an F16 table."""
         buf = gguf if isinstance(gguf, np.ndarray) else np.frombuffer(gguf, np.uint8)
         buf = np.ascontiguousarray(buf)
         self._tp_id = C.create_string_buffer(bytes(tp_id), TP_ID_BYTES) if tp_id is not None else None
@@ -224,7 +228,7 @@ class Model:
             raise ValueError(f"tp_id must be {TP_ID_BYTES} bytes")
         self._tp_group = tp_group  # keep the group alive as long as the session
         flags = (LLMI_EXACT if exact else 0) | (0 if use_graph else LLMI_NO_GRAPH) | (LLMI_TP_PEER if tp_peer else 0) | \
-            (LLMI_EXACT_KQ if exact_kq else 0)
+            (LLMI_EXACT_KQ if exact_kq else 0) | (LLMI_BATCH_QTABLE if batch_qtable else 0)
         opts = SessionOpts(device, flags,
                            max_ctx, attn_split, tp_rank, tp_size,
                            C.cast(self._tp_id, C.c_void_p) if self._tp_id is not None else None,

@@ -245,6 +245,31 @@ def logits_rows_rb(E: int) -> int:
     return int(lib().llmi_logits_rows_rb(int(E)))
 
 
+def logits_rows_q8(x, wq, softcap: float = 0.0) -> np.ndarray:
+    """llmi_logits_rows_q8: the multi-row Q8_0 x Q8_0 logits GEMV alone.  x [T][E] float32
+    rows, quantized on the device to Q8_0 blocks; wq: the table's V rows of GGUF Q8_0 blocks (uint8, V x E / 32 x
+    34 B).  Returns float32 [T][V]: row t carries the bits of the fast Q8_0 mat_vec_mul of wq with x[t] alone, then
+    cap tanh(l / cap) when softcap > 0.  E % 32 != 0 raises (LLMI_E_SIZE)."""
+    xa = np.ascontiguousarray(x, np.float32)
+    wb = np.ascontiguousarray(wq).view(np.uint8).reshape(-1)
+    if xa.ndim != 2:
+        raise ValueError("logits_rows_q8: x [T][E]")
+    T, E = xa.shape
+    row_bytes = E // 32 * 34
+    if E % 32 == 0 and E > 0 and wb.size % row_bytes != 0:
+        raise ValueError("logits_rows_q8: wq must hold whole rows of E / 32 Q8_0 blocks")
+    V = wb.size // row_bytes if E % 32 == 0 and E > 0 else 1
+    out = np.zeros((max(T, 0), V), np.float32)
+    check(lib().llmi_logits_rows_q8(ptr(xa), ptr(wb), T, V, E, float(softcap), ptr(out)))
+    return out
+
+
+def logits_rows_q8_rb(E: int) -> int:
+    """llmi_logits_rows_q8_rb: the activation rows that share one read of the table in logits_rows_q8 at width E
+    (0: the width is not supported).  No GPU work."""
+    return int(lib().llmi_logits_rows_q8_rb(int(E)))
+
+
 def gemm_rows_plan(n_rows: int, n_cols: int, T: int) -> int:
     """llmi_gemm_rows_plan: the kernel gemm_rows(kernel="auto") and the session run for a Q4_0 weight [n_rows][n_cols]
     at T token rows -- 1 the skinny kernel, 6 / 7 the tiled ones, 0 unsupported.  No GPU work."""

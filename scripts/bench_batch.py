@@ -76,6 +76,58 @@ def shared(a, cfg, g):
     print(json.dumps({"config": cfg.name, "mode": "shared", "steps": a.steps, "repeats": a.repeats, "rows": rows}))
 
 
+def qtable(a):
+    """--table q8_0: Gemma-3 1B with Q8_0 layers and a Q8_0 output table, batch_qtable on.
+    Per B, greedy and sampled: the step time with the multi-row logits launch and the rows reduce
+    (LLMI_BATCH_QTABLE_ROWS=1: at every B) and with one launch_gemv + one row reduce per row (=0), interleaved."""
+    from llm_inference_amd.gguf import TensorType as TT
+    from llm_inference_amd.model import Model
+    from llm_inference_amd.synthetic import CONFIGS, build_gemma3_gguf
+    cfg = CONFIGS["gemma-3-1b"]
+    batches = [int(b) for b in a.batches.split(",")]
+    m = Model(build_gemma3_gguf(cfg, seed=1234, wtype=TT.Q8_0, embd_type=TT.Q8_0), max_ctx=a.prefill + a.steps + 8,
+              batch_qtable=True)
+    rng = np.random.default_rng(1)
+    prompt = np.concatenate([[2], rng.integers(4, cfg.vocab, a.prefill - 1)]).astype(np.int32)
+    m.forward(prompt, 0, want_logits=False)
+    first, pos = m.last_argmax, a.prefill
+    m.reserve_sequences(max(batches))
+    for s in range(1, max(batches)):
+        m.copy_sequence(s, 0, a.prefill)
+    sp = dict(temperature=0.8, top_k=40, top_p=0.95, seed=7)
+
+    def run(B, steps, multi, sampled):
+        os.environ["LLMI_BATCH_QTABLE_ROWS"] = "1" if multi else "0"
+        m.sync()
+        t0 = time.perf_counter()
+        m.batch_generate([first] * B, list(range(B)), [pos] * B, steps, samplers=sp if sampled else None)
+        return (time.perf_counter() - t0) / steps * 1e6
+
+    rows = []
+    for B in batches:
+        for sampled in (False, True):
+            run(B, a.warmup, True, sampled), run(B, a.warmup, False, sampled)
+            on, off = [], []
+            for _ in range(a.repeats):
+                off.append(run(B, a.steps, False, sampled))
+                on.append(run(B, a.steps, True, sampled))
+            r = {"B": B, "mode": "sampled" if sampled else "greedy",
+                 "step_us_multi": round(med(on), 1), "step_us_multi_min_max": [round(min(on), 1), round(max(on), 1)],
+                 "step_us_per_row": round(med(off), 1),
+                 "step_us_per_row_min_max": [round(min(off), 1), round(max(off), 1)],
+                 "step_speedup": round(med(off) / med(on), 3)}
+            if sampled:  # time_kernel(11): the logits launches + select + finalize over the last step's rows
+                for name, v in (("multi", "1"), ("per_row", "0")):
+                    os.environ["LLMI_BATCH_QTABLE_ROWS"] = v
+                    us, by = m.time_kernel(11, a.kernel_reps)
+                    r["logits_select_us_" + name], r["logits_bytes_" + name] = round(us, 1), by
+            rows.append(r)
+    os.environ.pop("LLMI_BATCH_QTABLE_ROWS", None)
+    print(json.dumps({"config": cfg.name, "mode": "table q8_0", "prefill": a.prefill, "steps": a.steps,
+                      "repeats": a.repeats, "rows": rows}))
+    m.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--config", default="gemma-3-4b")
@@ -87,7 +139,11 @@ def main():
     p.add_argument("--batches", default=None)
     p.add_argument("--shared", action="store_true")
     p.add_argument("--prompts", default="512,2048")
+    p.add_argument("--table", default="f16", choices=["f16", "q8_0"])
     a = p.parse_args()
+    if a.table == "q8_0":
+        a.batches = a.batches or "1,8,32,64"
+        return qtable(a)
     a.batches = a.batches or ("8,32,64" if a.shared else "1,2,4,8,16,32,64")
     from llm_inference_amd.model import Model
     from llm_inference_amd.synthetic import CONFIGS, build_gemma3_gguf
